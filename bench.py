@@ -16,7 +16,11 @@ Workloads (BASELINE.json configs):
 synchronize on both sides).  `--gpus N` without WORLD_SIZE starts the N rank processes itself
 (torch.distributed.run on 127.0.0.1) before any GPU call; under torchrun WORLD_SIZE must equal N.
 
-Extra fields (rank 0, N = 1): the drop-in rate (Twist::prove on host buffers through the C ABI,
+A plain run sets up, warms up, times its --steps steps, writes the last step's proof if
+--dump-outputs DIR is given (DIR/<name>.npy, see dump_outputs) and prints the result line; the
+timed steps carry no HIP events.  Everything below runs only with --full.
+
+Extra fields (--full; rank 0, N = 1): the drop-in rate (Twist::prove on host buffers through the C ABI,
 PCIe included, over the same steps), the coefficient route (interpolation + coefficient KZG: the
 only route for an SRS without tau, src/utils.rs:107), C2 MSM pairs/s at 2^20 (setup_params(18),
 Fr::rand scalars from ChaCha20Rng([7;32])), C3 Shout lookups/s (2^20-entry table, 2^20 lookups),
@@ -66,7 +70,16 @@ def parse():
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument("--strong", action="store_true", help="C5 (one 2^26-op proof) at every N, N = 1 included")
     mode.add_argument("--weak", action="store_true", help="2^24 operations per GPU: one N * 2^24-op proof")
-    ap.add_argument("--no-extras", action="store_true", help="skip C2/C3 extras and the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything else the benchmark measures or checks: the roofline "
+                         "kernel's HIP events inside the timed steps, the per-stage steps, the clock probe, the "
+                         "drop-in / coefficient / no-table routes, C2, C3, C5 on one GPU, the tau-free route, the "
+                         "generic sum-check and the CPU baselines (N > 1: the sharded C2 MSM)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proof the last timed step returned as DIR/<name>.npy "
+                         "(float64; every field element as 16 limbs of 16 bits, least significant first)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip C2/C3 extras and the CPU baseline (roofline and stages stay)")
     ap.add_argument("--cpu-ref-logs", default="4-9",
                     help="reference-algorithm oracle: time one proof at each 2^k ops, k in this range (a-b); "
                          "the O(N^3) time is fitted by a power law and extrapolated to 2^24 (labelled)")
@@ -114,7 +127,10 @@ def parse():
                          "the timed steps time only the roofline kernel (two HIP events per launch)")
     ap.add_argument("--profile-all-timed", action="store_true",
                     help="A/B: time every stage inside the timed steps (the pre-round-2 behaviour)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -617,6 +633,42 @@ def timed_proofs(fn, steps, warmup):
     return (time.perf_counter() - t0) / max(1, steps)
 
 
+def _limbs16(values):
+    """Integers below 2^256 -> float64 array (len, 16): 16-bit limbs, least significant first (exact)."""
+    out = np.zeros((len(values), 16), dtype=np.float64)
+    for i, v in enumerate(values):
+        for j in range(16):
+            out[i, j] = (v >> (16 * j)) & 0xFFFF
+    return out
+
+
+def dump_outputs(ts, raw, directory):
+    """--dump-outputs: the proof one timed step returned (the C proof struct of
+    tns_twist_prove_device / tns_twist_prove_sharded), field by field as DIR/<name>.npy.  Fr and Fq
+    values are canonical (out of Montgomery form); a G1 point is its affine (x, y), the point at
+    infinity (0, 0).  A few KB in all; the inputs (setup_params' ChaCha20 seed, the
+    src/benchmarks.rs:88-99 trace) are the same every run, so two builds compare array for array."""
+    p = ts.twist_proof_from_raw(raw)
+
+    def points(ps):
+        return _limbs16([c for P in ps for c in (P if P is not None else (0, 0))]).reshape(len(ps), 2, 16)
+
+    rounds = p.consistency_proof.round_polynomials
+    arrays = {
+        "commitments": points([p.address_commitment.commitment, p.value_commitment.commitment]),
+        "round_polynomials": _limbs16([c for r in rounds for c in r]).reshape(len(rounds), 4, 16),
+        "final_evaluation": _limbs16([p.consistency_proof.final_evaluation]),
+        "opening_proofs": points([q.proof for q in p.opening_proofs]),
+        "final_evaluations": _limbs16(p.final_evaluations),
+        "opening_point": _limbs16([p.opening_point] if p.opening_point is not None else []),
+        "sumcheck_challenges": _limbs16(p.sumcheck_challenges),
+        "final_mle_evals": _limbs16(p.final_mle_evals),
+    }
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -692,28 +744,33 @@ def main():
         prove()
     barrier_sync(pg, local)
     dstate = DeviceState(ts, local)
-    ts.profile_enable(ctx, True)
-    ts.profile_only(ctx, None if args.profile_all_timed else ROOF_KERNEL)
+    if args.full:  # a plain run puts no HIP events into its timed steps
+        ts.profile_enable(ctx, True)
+        ts.profile_only(ctx, None if args.profile_all_timed else ROOF_KERNEL)
     cs0 = comm.stats() if sharded else None
     dstate.start()
     t0 = time.perf_counter()
     for step in range(args.steps):
         if sharded and step == 0 and rank == args.stall_rank and args.stall_s > 0:
             time.sleep(args.stall_s)  # (--stall-rank: rehearse the exchange deadline)
-        prove()
+        last = prove()
     barrier_sync(pg, local)
     dt = time.perf_counter() - t0
     dstate.stop()
-    try:  # the clock the card holds under the accumulation's kind of load, right after the steps
-        dstate.valu_clock = ts.clock_probe(ctx, 60.0)
-    except Exception as e:  # diagnostic only
-        dstate.valu_clock = {"error": str(e)}
+    if args.dump_outputs and rank == 0:  # (sharded: every rank returns the one proof)
+        dump_outputs(ts, last, args.dump_outputs)
+    if args.full:
+        try:  # the clock the card holds under the accumulation's kind of load, right after the steps
+            dstate.valu_clock = ts.clock_probe(ctx, 60.0)
+        except Exception as e:  # diagnostic only
+            dstate.valu_clock = {"error": str(e)}
     if sharded:
         comm_cfg["per_rank"] = per_rank_exchange_record(pg, rank, dt, args.steps, cs0, comm.stats())
         comm_cfg["exchange_timeout_s"] = args.exchange_timeout
     breakdown = ctx.timing()
-    roof, stages = roofline_from_profile(ts, ctx)
-    clk = dstate.valu_clock.get("median_mhz") if isinstance(dstate.valu_clock, dict) else None
+    roof, stages = roofline_from_profile(ts, ctx) if args.full else (None, {})
+    valu_clock = getattr(dstate, "valu_clock", None)
+    clk = valu_clock.get("median_mhz") if isinstance(valu_clock, dict) else None
     if roof is not None and "compute" in roof and clk:
         # the pair peak scales with the VALU clock (DVFS under the power cap moves it box to box by
         # several %): the fraction at the clock this box held right after the timed steps
@@ -723,7 +780,7 @@ def main():
         cp["mac_carry_pair_peak_at_clock"] = round(peak_here, 3)
         cp["frac_of_pair_peak_at_clock"] = round(cp["achieved"] / peak_here, 4)
     stage_steps = args.steps
-    if not args.profile_all_timed and args.stage_steps > 0:  # every stage, on untimed steps
+    if args.full and not args.profile_all_timed and args.stage_steps > 0:  # every stage, on untimed steps
         ts.profile_enable(ctx, True)
         ts.profile_only(ctx, None)
         for _ in range(args.stage_steps):
@@ -731,8 +788,9 @@ def main():
         barrier_sync(pg, local)
         stages = read_stages(ts, ctx)
         stage_steps = args.stage_steps
-    ts.profile_only(ctx, None)
-    ts.profile_enable(ctx, False)
+    if args.full:
+        ts.profile_only(ctx, None)
+        ts.profile_enable(ctx, False)
     dt_max = max_over_ranks(pg, local, dt)
     total_ops = (n_total if sharded else world * n_ops) * args.steps
     value = total_ops / dt_max
@@ -750,6 +808,7 @@ def main():
     out = {
         "metric": METRIC, "value": round(value, 2), "unit": "ops/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(dt_max / args.steps * 1e3, 3), "higher_is_better": True,
+        "full": args.full,
         "scaling": scaling, "vs_baseline": None, "dtype": "u256 (8x u32 Montgomery, BN254 Fr/Fq)",
         "data": "synthetic (src/benchmarks.rs:88-99 trace)",
         "config": {"workload": workload, "log_ops": log_total, "ops_per_gpu": n_ops, "ops_per_proof": n_total,
@@ -763,7 +822,8 @@ def main():
         "setup_ms": {"setup_params": round(t_setup * 1e3, 1), "lagrange_basis": round(t_lag * 1e3, 1)},
         "device_state": dstate.record(),
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    extras = args.full and not args.no_extras
+    if rank == 0 and world == 1 and extras:
         # drop-in rate: Twist::prove on host buffers through the C ABI (PCIe and host-side SoA
         # included), the same number of steps (SURVEY 8(d) measures prove() on host data); the
         # raw proof struct is what a Rust binding receives, so the Python mirror's proof objects
@@ -829,22 +889,22 @@ def main():
         t_sh = timed_proofs(lambda: ts.shout_prove_resident(pp18, d_e, T, d_i, T), 5, 1)
         out["shout_lookups_per_sec_2^20"] = round(T / t_sh, 1)
         out["shout_ms_2^20"] = round(t_sh * 1e3, 3)
-    if rank == 0 and world == 1 and not args.no_extras and args.c5_steps > 0 and log_total == 24:
+    if rank == 0 and world == 1 and extras and args.c5_steps > 0 and log_total == 24:
         out["c5_one_gpu"] = c5_one_gpu(ts, ctx, local, args.c5_steps)
         out["c5_one_gpu_ms_per_step"] = out["c5_one_gpu"].get("ms_per_step")
-    if sharded and not args.no_extras:  # the MSM half of the metric at N GPUs (C2 sharded)
+    if sharded and extras:  # the MSM half of the metric at N GPUs (C2 sharded)
         with exchange_guard(ts, rank, "KZG MSM 2^20 (sharded)"):
             out.update(sharded_msm(ts, ctx, comm, pg, local, rank, world))
-    if rank == 0 and world == 1 and not args.no_extras and args.tau_free_log > 0:
+    if rank == 0 and world == 1 and extras and args.tau_free_log > 0:
         out["tau_free_route"] = tau_free_route(ts, ctx, args.tau_free_log)
-    if rank == 0 and world == 1 and not args.no_extras and args.sumcheck_logs:
+    if rank == 0 and world == 1 and extras and args.sumcheck_logs:
         out["sumcheck_generic"] = sumcheck_generic(ts, ctx, [int(x) for x in args.sumcheck_logs.split(",")])
     if roof is not None:
         out["roofline"] = roof
         out["stages_ms_per_step"] = {k: round(v["ms"] / stage_steps, 3) for k, v in stages.items()}
         out["stages_timed_on"] = ("the timed steps" if args.profile_all_timed or args.stage_steps <= 0
                                   else f"{stage_steps} untimed steps after the timed region")
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         out["cpu_baseline"] = cpu_baseline(ts, ctx, args.cpu_fast_log_ops, args.cpu_threads, pp=pp)
         lo, hi = (int(x) for x in args.cpu_ref_logs.split("-"))
         out["cpu_reference_algorithms"] = cpu_reference_algorithms(range(lo, hi + 1))

@@ -11,7 +11,7 @@ mkdir -p $out
 for rep in $(seq 1 $reps); do
   for v in default "$@"; do
     if [ $v = default ]; then lib=$L/libtns.so; else lib=$L/libtns_$v.so; fi
-    TNS_LIB=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 3 --coef-steps 0 --tau-free-log 0 --sumcheck-logs "" \
+    TNS_LIB=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 3 --coef-steps 0 --tau-free-log 0 --sumcheck-logs "" \
       --c5-steps 0 --no-table-steps 0 --cpu-ref-logs 4-4 --cpu-fast-log-ops 14 > $out/b_${v}_$rep.jsonl 2> $out/b_${v}_$rep.err || { tail -5 $out/b_${v}_$rep.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$out/b_${v}_$rep.jsonl').read().strip().splitlines()[-1])
@@ -21,7 +21,7 @@ done
 port=29571
 for v in "$@"; do
   TNS_LIB=$L/libtns_$v.so timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-    --master-port $port bench.py --gpus 4 --steps 3 --warmup 1 --rehearse-one-gpu > $out/rehearse4_$v.jsonl 2> $out/rehearse4_$v.err || { tail -20 $out/rehearse4_$v.err; exit 1; }
+    --master-port $port bench.py --full --gpus 4 --steps 3 --warmup 1 --rehearse-one-gpu > $out/rehearse4_$v.jsonl 2> $out/rehearse4_$v.err || { tail -20 $out/rehearse4_$v.err; exit 1; }
   port=$((port + 1))
   python3 -c "
 import json; r=json.loads(open('$out/rehearse4_$v.jsonl').read().strip().splitlines()[-1])

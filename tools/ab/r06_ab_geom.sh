@@ -9,7 +9,7 @@ TNS_LIB=$L/libtns_$1.so timeout -k 10 600 python3 -u -m pytest -x -q --timeout 1
 tail -1 $out/tests_$1.txt
 bash tools/ab/r06_ab_lib.sh geom 4 "$@" || exit 1
 for v in "$@"; do
-  TNS_LIB=$L/libtns_$v.so timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/tr_$v -o run --output-format csv -- python3 bench.py --no-extras --steps 2 --warmup 1 > $out/tr_$v.log 2>&1 || exit 1
+  TNS_LIB=$L/libtns_$v.so timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/tr_$v -o run --output-format csv -- python3 bench.py --full --no-extras --steps 2 --warmup 1 > $out/tr_$v.log 2>&1 || exit 1
   f=$(find $out/tr_$v -name "run_kernel_trace.csv" | head -n 1)
   python3 tools/trace_tail.py "$f" k_u64_tables 0.05 > $out/timeline_$v.txt 2>&1
 done

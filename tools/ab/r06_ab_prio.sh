@@ -12,7 +12,7 @@ port=29561
 for v in default "$@"; do
   if [ $v = default ]; then lib=$L/libtns.so; else lib=$L/libtns_$v.so; fi
   TNS_LIB=$lib timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-    --master-port $port bench.py --gpus 4 --steps 3 --warmup 1 --rehearse-one-gpu > $out/rehearse4_$v.jsonl 2> $out/rehearse4_$v.err || { tail -20 $out/rehearse4_$v.err; exit 1; }
+    --master-port $port bench.py --full --gpus 4 --steps 3 --warmup 1 --rehearse-one-gpu > $out/rehearse4_$v.jsonl 2> $out/rehearse4_$v.err || { tail -20 $out/rehearse4_$v.err; exit 1; }
   port=$((port + 1))
   python3 -c "
 import json; r=json.loads(open('$out/rehearse4_$v.jsonl').read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ tag=$1; norh=${2:-}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r06_full_$tag
 mkdir -p $out
-timeout -k 10 400 python3 -u bench.py --steps 20 --warmup 5 > $out/bench.jsonl 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 400 python3 -u bench.py --full --steps 20 --warmup 5 > $out/bench.jsonl 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 python3 - "$out/bench.jsonl" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -18,7 +18,7 @@ print("cpu", (d.get("cpu_baseline") or {}).get("value"), "roof", d["roofline"].g
 PY
 [ -n "$norh" ] && exit 0
 timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-  --master-port 29541 bench.py --gpus 4 --steps 3 --warmup 1 --rehearse-one-gpu > $out/rehearse4.jsonl 2> $out/rehearse4.err || { tail -20 $out/rehearse4.err; exit 1; }
+  --master-port 29541 bench.py --full --gpus 4 --steps 3 --warmup 1 --rehearse-one-gpu > $out/rehearse4.jsonl 2> $out/rehearse4.err || { tail -20 $out/rehearse4.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$out/rehearse4.jsonl').read().strip().splitlines()[-1])
 print('rehearse4', d['ms_per_step'], d['value'], [(r['exchanges_per_step'], r['mean_exchange_us'], r['mean_exchange_bytes_per_rank']) for r in d['comm']['per_rank']])"

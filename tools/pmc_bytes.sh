@@ -6,5 +6,5 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for c in FETCH_SIZE WRITE_SIZE; do
   out=gpurun_out/pmcb_${tag}_$c
   mkdir -p $out
-  timeout -s KILL 300 rocprofv3 --pmc $c -d $out -o run --output-format csv -- python3 bench.py --no-extras --steps 1 --warmup 0 > $out/bench.log 2>&1
+  timeout -s KILL 300 rocprofv3 --pmc $c -d $out -o run --output-format csv -- python3 bench.py --full --no-extras --steps 1 --warmup 0 > $out/bench.log 2>&1
 done

@@ -4,7 +4,7 @@
     python tools/pmc_summary.py gpurun_out/prof_<tag> <steps_total> > profiles/pmc_traffic.json
 
 steps_total: every proof the profiled bench ran -- warmup + steps + its untimed stage steps
-(--stage-steps, default 2): `bench.py --no-extras --steps 2 --warmup 1` runs 5.
+(--stage-steps, default 2): `bench.py --full --no-extras --steps 2 --warmup 1` runs 5.
 
 FETCH_SIZE / WRITE_SIZE are in KiB.  Correction per MI355X_MICROARCH.md (HBM section):
 FETCH_SIZE on gfx950 reports half the bytes of wide coalesced reads -> x2; WRITE_SIZE as is.
