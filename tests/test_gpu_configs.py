@@ -59,15 +59,24 @@ def replay(seed, labels, C0, C1, nv):
     return chals, t.challenge_field_element(b"opening_challenges_0")
 
 
+def eval_pair(w, n, y0, y1, x, T):
+    """(f0(x), f1(x), ell(x)) of the interpolants of two (n, 4) Montgomery vectors on the nodes
+    0..n-1: barycentric off the nodes; at a node x < n they take their entries y[x] (ell = 0)."""
+    if x < n:
+        return co.fr_ints(np.asarray(y0)[x])[0], co.fr_ints(np.asarray(y1)[x])[0], 0
+    return co.bary_eval2(w, y0, y1, x, T)
+
+
 def check_pair(tau, n, y0, y1, commitments, z, values, proofs):
     """Both commitments and both openings of a proof against the trapdoor identities; returns the
-    barycentric weights and ell(tau) for the basis spot check."""
+    barycentric weights and ell(tau) for the basis spot check.  tau may be a node (an uploaded SRS)
+    and any of the points the identity."""
     w = co.bary_weights(n)
     T = host_threads()
-    f0t, f1t, ell_t = co.bary_eval2(w, y0, y1, tau, T)
+    f0t, f1t, ell_t = eval_pair(w, n, y0, y1, tau, T)
     assert commitments[0] == co.g1_mul_gen(f0t)
     assert commitments[1] == co.g1_mul_gen(f1t)
-    f0z, f1z, _ = co.bary_eval2(w, y0, y1, z, T)
+    f0z, f1z, _ = eval_pair(w, n, y0, y1, z, T)
     assert list(values) == [f0z, f1z]
     for C, v, pi in zip(commitments, values, proofs):
         assert co.g1_mul(pi, (tau - z) % R) == po.affine_add(C, po.g1_neg(co.g1_mul_gen(v)))
