@@ -1,0 +1,111 @@
+// abi.hpp -- what the translation units of the C ABI (api.hip, kzg.hip, prove.hip, abi_host.cpp)
+// share: the opaque handle types of include/tns.h, the error guard of every entry point, and the
+// KZG routes of kzg.hip.
+#pragma once
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+
+struct tns_ctx {
+  tns::Ctx c;
+  double timing[6] = {0, 0, 0, 0, 0, 0};
+};
+struct tns_srs {
+  tns::Srs s;
+};
+struct tns_transcript {
+  tns::HostTranscript t;
+};
+struct tns_comm {
+  tns::Comm *c = nullptr;
+  ~tns_comm() { delete c; }
+};
+struct tns_buffer {
+  tns::DevBuf buf;
+  size_t bytes = 0;
+  int device = 0;
+};
+
+namespace tns {
+
+template <class F>
+static int guarded(F &&f) {
+  try {
+    return f();
+  } catch (const Error &e) {
+    set_last_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return TNS_ERR_DEVICE;
+  }
+}
+
+static void store_proj(const G1Affine &a, uint64_t out[12]) {
+  G1Jac j = affine_to_jac(a);
+  std::memcpy(out, &j, sizeof j);
+}
+static G1Affine proj_to_affine_host(const uint64_t in[12]) {
+  G1Jac j;
+  std::memcpy(&j, in, sizeof j);
+  G1Affine a;
+  if (j.z.is_zero()) {
+    a.x = Fq::zero();
+    a.y = Fq::zero();
+    return a;
+  }
+  Fq zi = inv(j.z), zi2 = sqr(zi);
+  a.x = mul(j.x, zi2);
+  a.y = mul(j.y, mul(zi2, zi));
+  return a;
+}
+
+struct Timer {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+};
+
+// One committed vector of Twist/Shout::prove: evaluations y on the nodes 0..N-1
+// (vector_to_polynomial input, src/polynomials.rs:248-262), of which this rank holds the
+// slice [first, first + cnt).  Committed and opened via the Lagrange basis when the SRS
+// provides it (partial MSMs summed over the ranks), else via interpolated coefficients.
+struct EvalPoly {
+  const Fr *y = nullptr;       // device, cnt (must stay intact until opened)
+  Fr *coeffs = nullptr;        // device scratch, N (coefficient path, unsharded only)
+  size_t N = 0, first = 0, cnt = 0;
+  const LagrangeBasis *basis = nullptr;
+  bool have_coeffs = false;
+};
+
+// What rides along with an exchange of MSM partials (the exchanges of a sharded proof are few and
+// latency-bound, so independent payloads share one): `bytes` of this rank's data, every rank's
+// copy landing rank-major in `all` (size * bytes).
+struct ExtraPayload {
+  const void *data = nullptr;
+  size_t bytes = 0;  // a multiple of 4
+  std::vector<uint8_t> all;
+};
+
+// kzg.hip
+G1Affine commit_dev(Ctx *c, const Srs &srs, const Fr *coeffs, size_t n);
+void open_dev(Ctx *c, const Srs &srs, const Fr *coeffs, size_t n, const Fr &z, Fr *value, G1Affine *proof,
+              DevBuf &sbuf);
+G1Affine commit_evals(Ctx *c, const Srs &srs, EvalPoly &p, Comm &m);
+void open_evals(Ctx *c, const Srs &srs, EvalPoly &p, const Fr &z, Fr *value, G1Affine *proof, DevBuf &sbuf, Comm &m);
+void commit_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, Comm &m, G1Affine out[2],
+                       const ScalarSource *src0 = nullptr, const ScalarSource *src1 = nullptr,
+                       ExtraPayload *extra = nullptr);
+void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const Fr &z, Fr value[2], G1Affine proof[2],
+                     DevBuf &sbuf0, DevBuf &sbuf1, Comm &m, ExtraPayload *extra = nullptr,
+                     const std::function<void()> &extra_ready = nullptr,
+                     const std::function<void()> &side_work = nullptr);
+// prove.hip
+void check_shard(const Comm &m, size_t N, const char *what);
+size_t slice_count(uint64_t n_total, size_t first, size_t L);
+
+}  // namespace tns

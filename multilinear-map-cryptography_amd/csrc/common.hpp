@@ -45,6 +45,23 @@ void set_last_error(const std::string &msg);
 
 #define TNS_LAUNCH_CHECK() TNS_HIP(hipGetLastError())
 
+// A HIP event that lives as long as its scope (ordering only unless flags say otherwise).
+struct Event {
+  hipEvent_t e = nullptr;
+  explicit Event(unsigned flags = hipEventDisableTiming) { TNS_HIP(hipEventCreateWithFlags(&e, flags)); }
+  Event(const Event &) = delete;
+  Event &operator=(const Event &) = delete;
+  ~Event() { (void)hipEventDestroy(e); }
+  operator hipEvent_t() const { return e; }
+};
+
+// `waiter` runs nothing queued after this call before what is queued on `producer` so far is done
+inline void stream_wait(hipStream_t waiter, hipStream_t producer) {
+  Event ready;
+  TNS_HIP(hipEventRecord(ready, producer));
+  TNS_HIP(hipStreamWaitEvent(waiter, ready, 0));
+}
+
 // Grow-only device allocation (never shrinks; freed with the context).
 struct DevBuf {
   void *p = nullptr;
@@ -496,26 +513,8 @@ __device__ __forceinline__ void block_atomic_max2(unsigned b0, unsigned b1, unsi
     if (b1 && dst1) atomicMax(dst1, b1);
   }
 }
-struct MsmArgs {
-  const G1Affine *points;
-  const Fr *scalars;
-  size_t n;
-  const FixedBase *fb;
-  // set: the scalars' largest bit length is at this device address and the sort reads
-  // canonical scalars -- `canon` if set (then `scalars` stay Montgomery, for the tiny path),
-  // else `scalars` themselves (n > 64 only: the tiny path reads Montgomery scalars)
-  const unsigned *canon_bits = nullptr;
-  const Fr *canon = nullptr;
-  // set (with canon_bits, canonical scalars): pass 1's histograms are precounted (SortInput::precounted)
-  const uint32_t *precounted = nullptr;
-  int pre_c = 0, pre_W = 0;
-  // > 0: plan the MSM for scalars of this bit length without reading canon_bits back (the opening
-  // quotients: full width -- the table plan's extra windows of a narrower quotient carry no digits,
-  // so the entries are the same); the sort can be queued right behind the kernel writing the scalars
-  int plan_bits = 0;
-  // set (with canon_bits): the sort reads these raw u64 values (entries [0, n_u64)) instead
-  const uint64_t *u64 = nullptr;
-  size_t n_u64 = 0;
+// how the scalars of one MSM of a pair get ready and in which form the sort reads them
+struct ScalarSource {
   // enqueued on the lane's stream before anything else of this MSM: produces the scalars
   // (and canon / canon_bits) without holding up the other lane
   std::function<void(hipStream_t)> prep;
@@ -529,18 +528,28 @@ struct MsmArgs {
   int chunks = 0;
   std::vector<size_t> chunk_off;  // chunks + 1 offsets, increasing, chunk_off[chunks] = n
   std::function<void(int, hipStream_t)> chunk_prep;
-};
-// how one vector of commit_evals_pair gets ready (the MsmArgs fields of the same names)
-struct ScalarSource {
-  std::function<void(hipStream_t)> prep;
-  bool late = false;
-  int chunks = 0;                                   // (MsmArgs::chunks, chunk_off, chunk_prep)
-  std::vector<size_t> chunk_off;
-  std::function<void(int, hipStream_t)> chunk_prep;
+  // set: the scalars' largest bit length is at this device address and the sort reads
+  // canonical scalars -- `canon` if set (then `scalars` stay Montgomery, for the tiny path),
+  // else `scalars` themselves (n > 64 only: the tiny path reads Montgomery scalars)
   const Fr *canon = nullptr;
   const unsigned *canon_bits = nullptr;
+  // set (with canon_bits): the sort reads these raw u64 values (entries [0, n_u64)) instead
   const uint64_t *u64 = nullptr;
   size_t n_u64 = 0;
+};
+struct MsmArgs {
+  const G1Affine *points;
+  const Fr *scalars;
+  size_t n;
+  const FixedBase *fb;
+  // set (with src.canon_bits, canonical scalars): pass 1's histograms are precounted (SortInput::precounted)
+  const uint32_t *precounted = nullptr;
+  int pre_c = 0, pre_W = 0;
+  // > 0: plan the MSM for scalars of this bit length without reading src.canon_bits back (the opening
+  // quotients: full width -- the table plan's extra windows of a narrower quotient carry no digits,
+  // so the entries are the same); the sort can be queued right behind the kernel writing the scalars
+  int plan_bits = 0;
+  ScalarSource src;
 };
 // two independent MSMs overlapped on the context's two lanes (inputs ready on c->stream)
 void msm_pair_dev(Ctx *c, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]);

@@ -1110,40 +1110,36 @@ G1Xyzz msm_dev(Ctx *ctx, const G1Affine *points, const Fr *scalars, size_t n, co
   return msm_complete(ctx, J);
 }
 
-void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
-  if (a.late && !b.late) {  // the late vector goes second (lane 1)
+static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
+  if (a.src.late && !b.src.late) {  // the late vector goes second (lane 1)
     G1Xyzz o[2];
-    msm_pair_dev(ctx, b, a, o);
+    msm_pair_queue(ctx, b, a, o);
     out[0] = o[1];
     out[1] = o[0];
     return;
   }
   MsmLane &l0 = ctx->lanes[0], &l1 = ctx->lanes[1];
   // lane 1 starts after everything already queued on the context stream (its inputs)
-  hipEvent_t ready;
-  TNS_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-  TNS_HIP(hipEventRecord(ready, ctx->stream));
-  TNS_HIP(hipStreamWaitEvent(l1.stream, ready, 0));
-  (void)hipEventDestroy(ready);
+  stream_wait(l1.stream, ctx->stream);
   unsigned ba = 254, bb = 254;
   SortInput ca, cb;
   // canonical inputs (the opening quotients) and raw u64 inputs (trace addresses, lookup
   // indices) come with their bit lengths on the device
   auto start = [&](MsmLane &ln, const MsmArgs &x) -> SortInput {
-    if (x.prep) x.prep(ln.stream);
+    if (x.src.prep) x.src.prep(ln.stream);
     if (x.n <= 64) return SortInput();
-    if (!x.canon_bits) return bits_launch(ln, x.scalars, x.n);
+    if (!x.src.canon_bits) return bits_launch(ln, x.scalars, x.n);
     if (x.plan_bits <= 0) {  // (plan_bits: nothing to read back)
-      const void *src[1] = {x.canon_bits};
+      const void *src[1] = {x.src.canon_bits};
       const size_t by[1] = {sizeof(unsigned)};
       lane_publish(ln, LANE_SLOT_BITS, 1, src, by);
     }
     SortInput in;
-    if (x.u64) {
-      in.u64 = x.u64;
-      in.n_u64 = x.n_u64;
+    if (x.src.u64) {
+      in.u64 = x.src.u64;
+      in.n_u64 = x.src.n_u64;
     } else {
-      in.fr = x.canon ? x.canon : x.scalars;
+      in.fr = x.src.canon ? x.src.canon : x.scalars;
       in.precounted = x.precounted;
       in.pre_c = x.pre_c;
       in.pre_W = x.pre_W;
@@ -1151,7 +1147,7 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
     return in;
   };
   MsmJob ja, jb;
-  if (b.late) {
+  if (b.src.late) {
     // b's scalars are still being uploaded (HostUpload, a helper thread): a's MSM is queued whole
     // first -- sort, accumulation, tail -- so it runs under the upload; b's prep then waits for
     // the upload and b's MSM follows on lane 1
@@ -1159,15 +1155,16 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
     if (a.n > 64) ba = bits_result(l0);
     msm_launch_sort(ctx, l0, a.points, a.scalars, ca, a.n, a.fb, ba, ja);
     msm_launch_reduce(ctx, ja);
-    if (b.chunks > 1) {  // one MSM per uploaded chunk, each as soon as it lands
-      if ((int)b.chunk_off.size() != b.chunks + 1 || b.chunk_off.back() != b.n)
+    if (b.src.chunks > 1) {  // one MSM per uploaded chunk, each as soon as it lands
+      const ScalarSource &bs = b.src;
+      if ((int)bs.chunk_off.size() != bs.chunks + 1 || bs.chunk_off.back() != b.n)
         throw Error(TNS_ERR_INVALID_PARAMETERS, "chunk offsets do not cover the scalars");
       G1Xyzz acc = G1Xyzz::inf();
-      for (int k = 0; k < b.chunks; k++) {
-        const size_t off = b.chunk_off[k], cnt = b.chunk_off[k + 1] - off;
+      for (int k = 0; k < bs.chunks; k++) {
+        const size_t off = bs.chunk_off[k], cnt = bs.chunk_off[k + 1] - off;
         if (!cnt) continue;
-        MsmArgs bk{b.points + off, b.scalars + off, cnt, b.fb};
-        bk.prep = [&b, k](hipStream_t s) { b.chunk_prep(k, s); };
+        MsmArgs bk{b.points + off, b.scalars + off, cnt, b.fb};  // (Montgomery scalars: no canon_bits)
+        bk.src.prep = [&bs, k](hipStream_t s) { bs.chunk_prep(k, s); };
         MsmJob jk;
         unsigned bk_bits = 254;
         const SortInput ck = start(l1, bk);
@@ -1192,9 +1189,7 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
   cb = start(l1, b);
   if (a.n > 64) ba = a.plan_bits > 0 ? (unsigned)a.plan_bits : bits_result(l0);
   if (b.n > 64) bb = b.plan_bits > 0 ? (unsigned)b.plan_bits : bits_result(l1);
-  hipEvent_t sa = nullptr, sb = nullptr;
-  TNS_HIP(hipEventCreateWithFlags(&sa, hipEventDisableTiming));
-  TNS_HIP(hipEventCreateWithFlags(&sb, hipEventDisableTiming));
+  Event sa, sb;
   // both lanes' passes are queued before either lane's host wait (the last pass's readback), and
   // each lane's last pass follows its own readback: the two sorts run side by side and neither
   // waits for the other's first passes (profiles/r02_ab_sort_overlap.txt, r05_ab_sort_overlap.txt)
@@ -1202,9 +1197,9 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
   msm_sort_passes(ja);
   msm_launch_sort(ctx, l1, b.points, b.scalars, cb, b.n, b.fb, bb, jb, sb, true);
   msm_sort_passes(jb);
-  // Both accumulations go on the context's side stream (free here: its folds run before the
-  // openings' MSMs), one after the other (each is VALU-bound on the whole chip: run together they
-  // take as long), each as soon as its own sort is done: the first runs beside the rest of lane 1's
+  // Both accumulations go on the context's accumulation stream (ctx->acc, at the least priority:
+  // api.hip's create_streams), one after the other (each is VALU-bound on the whole chip: run together
+  // they take as long), each as soon as its own sort is done: the first runs beside the rest of lane 1's
   // sort, which then finishes in the first accumulation's tail-off.  Waiting for both sorts first
   // left the chip to lane 1's last passes alone for ~1.2 ms; this is 0.4 ms faster per C4 step
   // (profiles/r06_ab_acc_stream.txt) -- lane 1's sort stage then spans the first accumulation.
@@ -1215,9 +1210,7 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
   // is longer than the value accumulation).
   hipStream_t as = ctx->acc;
   msm_finish_sort(ja);
-  hipEvent_t acc_a, acc_b;
-  TNS_HIP(hipEventCreateWithFlags(&acc_a, hipEventDisableTiming));
-  TNS_HIP(hipEventCreateWithFlags(&acc_b, hipEventDisableTiming));
+  Event acc_a, acc_b;
   // a two-set tail needs the pair's buckets adjoining: room for both before acc a writes the first
   if (ja.sorted && ja.P.shared) ja.buckets = (G1Xyzz *)l0.ws[5].ensure(sizeof(G1Xyzz) * 2 * ja.P.nb);
   TNS_HIP(hipStreamWaitEvent(as, sa, 0));
@@ -1228,8 +1221,6 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
   if (two_set) jb.buckets = ja.buckets + ja.P.nb;
   TNS_HIP(hipStreamWaitEvent(as, sb, 0));
   msm_launch_accumulate(ctx, jb, acc_b, as);
-  (void)hipEventDestroy(sa);
-  (void)hipEventDestroy(sb);
   TNS_HIP(hipStreamWaitEvent(l0.stream, tails_last ? acc_b : acc_a, 0));
   if (two_set) {
     MsmJob *both[2] = {&ja, &jb};
@@ -1240,8 +1231,6 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
     msm_launch_tails(ctx, one_a, 1, l0);
     msm_launch_tails(ctx, one_b, 1, l1);
   }
-  (void)hipEventDestroy(acc_a);
-  (void)hipEventDestroy(acc_b);
   // two tails on two lanes: the host's part (bucket-sum Horner, ~20-45 us) of whichever lands
   // first runs while the other lane's tail still runs on the device
   if (!two_set && jb.res_lane && jb.res_lane != ja.res_lane && jb.sorted && ja.sorted) {
@@ -1258,6 +1247,19 @@ void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
   }
   out[0] = msm_complete(ctx, ja);
   out[1] = msm_complete(ctx, jb);
+}
+
+// When a pair fails part-way (a lane's wait, a HIP call, the chunk-offset check), nothing it queued
+// is still running once the error leaves: an accumulation left on ctx->acc would write lane 0's
+// buckets and fix-up flags under the context's next proof.  A pair that succeeds pays nothing.
+void msm_pair_dev(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {
+  try {
+    msm_pair_queue(ctx, a, b, out);
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx->acc);
+    for (MsmLane &ln : ctx->lanes) (void)hipStreamSynchronize(ln.stream);
+    throw;
+  }
 }
 
 }  // namespace tns

@@ -134,6 +134,31 @@ def test_shout_sharded_bad_index_fails_on_every_rank():
     assert all(isinstance(e, ts.InvalidParameters) for e in errs)
 
 
+def test_shout_sharded_proof_after_bad_index_on_the_same_context():
+    """A proof that failed after its commitment pair (two-lane sorted MSMs, the accumulation stream:
+    128 entries a rank, above the 64-entry tiny-MSM cutoff) leaves nothing behind on its context:
+    the next proof on the same context and communicator is the unsharded proof bit for bit."""
+    L, T, M, size = 10, 256, 256, 2
+    rng = np.random.default_rng(2560)
+    entries = ts.to_mont([int(x) for x in rng.integers(0, 2**62, size=T)])
+    idx = rng.integers(0, T, size=M, dtype=np.uint64)
+    bad = idx.copy()
+    bad[3] = T  # out of bounds, held by rank 0 only
+    want = ts.Shout(params(L)).prove_arrays(entries, idx)
+
+    def body(r, comm, ctx):
+        pp, _ = ts.setup_params_shard(L, r, size, ctx=ctx)
+        fe, ce = ts.shard_slice(T, r, size)
+        fi, ci = ts.shard_slice(M, r, size)
+        shout = ts.Shout(pp)
+        with pytest.raises(ts.InvalidParameters):
+            shout.prove_sharded(comm, entries[fe:fe + ce], T, bad[fi:fi + ci], M)
+        return shout.prove_sharded(comm, entries[fe:fe + ce], T, idx[fi:fi + ci], M)
+    got, errs = run_ranks(size, body)
+    assert errs == [None] * size
+    assert all(p == want for p in got)
+
+
 def test_sharded_shape_errors():
     L = 4
     addr, val, isw = ts.bench_trace(16, 64)
