@@ -159,6 +159,41 @@ int tns_srs_prepare_lagrange_from_powers(tns_ctx *ctx, tns_srs *srs, size_t n);
 /* Copy that basis ([L_j(tau)]G, j < n; built if needed) to host memory (affine uint64_t[8]
  * each): setup artefact for host-side provers (the CPU baseline of bench.py). */
 int tns_srs_lagrange_download(tns_ctx *ctx, tns_srs *srs, size_t n, uint64_t *g1_affine_out);
+/* SRS files.  The two setup artefacts as arkworks writes `Vec<G1Affine>` (ark-serialize 0.4:
+ * `params.commitment_params.g1_powers.serialize_compressed(&mut file)`): a u64 LE count, then 32
+ * bytes a point compressed or 64 uncompressed, in the point encoding of the wire-format section
+ * below.  Points are encoded, decoded and validated on the device (one Fq square root a compressed
+ * point).  All four calls take an unsharded SRS only (a shard -> TNS_ERR_INVALID_PARAMETERS), and
+ * a byte length that is not exactly the size the header's count implies -- truncated or with
+ * trailing bytes -- is TNS_ERR_INVALID_PARAMETERS. */
+/* 8 + n * (compressed ? 32 : 64) */
+size_t tns_srs_serialized_size(size_t n, int compressed);
+/* All of g1_powers.  out == NULL only sizes (*len set); cap too small -> TNS_ERR_INVALID_PARAMETERS
+ * with *len set (the contract of tns_proof_serialize). */
+int tns_srs_serialize(tns_ctx *ctx, const tns_srs *srs, int compressed, uint8_t *out, size_t cap, size_t *len);
+/* A new SRS from such bytes: like an uploaded one it has no tau (tns_srs_set_tau still attaches
+ * one) and builds its window table lazily -- but every point is validated as tns_g1_deserialize
+ * validates one: flags, coordinates below the modulus, on the curve.  The first bad point fails
+ * the call with TNS_ERR_INVALID_PARAMETERS and "G1 point <index>: <reason>".  A count of 0 gives
+ * an empty SRS. */
+int tns_srs_deserialize(tns_ctx *ctx, const uint8_t *in, size_t len, int compressed, tns_srs **out);
+/* The Lagrange basis [L_j(tau)]G, j < n, of the SRS in the same format (built if needed, as
+ * tns_srs_lagrange_download; same errors and buffer contract as tns_srs_serialize). */
+int tns_srs_lagrange_serialize(tns_ctx *ctx, tns_srs *srs, size_t n, int compressed, uint8_t *out, size_t cap,
+                               size_t *len);
+/* Attach a stored basis to an SRS -- what tns_srs_prepare_lagrange_from_powers computes, paid once
+ * and kept on disk.  n is the file's count: a power of two, with g1_powers[0..n) held.  The SRS
+ * has no tau to derive the basis from, so the file is checked against the powers before it is
+ * cached: with n scalars r expanded from `seed` (tns_fr_rand_batch's stream) and the coefficients
+ * c of r's interpolant on the nodes 0..n-1, sum_j r_j B_j must equal sum_i c_i g1_powers[i].  Any
+ * B other than the true basis passes for a fraction 1/|Fr| of the r only, PROVIDED r is not known
+ * to whoever wrote the file: pass seed == NULL (32 bytes drawn from the OS) unless the seed is
+ * chosen after the file and kept from its author; a fixed public seed checks nothing against an
+ * adversary.  Mismatch -> TNS_ERR_INVALID_PARAMETERS "Lagrange basis does not match g1_powers"
+ * and nothing is cached.  A basis already cached for n is kept (the file is still checked).
+ * Cost: one interpolation and two MSMs of n. */
+int tns_srs_lagrange_deserialize(tns_ctx *ctx, tns_srs *srs, const uint8_t *in, size_t len, int compressed,
+                                 const uint8_t seed[32]);
 /* Prove path selection: lagrange != 0 (default) commits/opens through the Lagrange
  * basis when the SRS has tau; 0 forces vector_to_polynomial + coefficient KZG
  * (src/twist.rs:151-163).  Both produce identical proofs. */
@@ -395,7 +430,8 @@ int tns_shout_prove_sharded(tns_ctx *ctx, const tns_srs *srs, const tns_params *
 /* ---------------------------------------------------------------- kernel timing */
 /* HIP-event timing of the named stages on the context stream ("msm_accumulate",
  * "msm_sort", "msm_digits", "msm_reduce", "ntt_stage", "ntt_lds", "ntt_pointwise",
- * "interp_tile", "sumcheck_round", "open_scan").  Enabling resets the totals and the stage
+ * "interp_tile", "sumcheck_round", "open_scan"; the SRS files' "g1_decode", "g1_encode").
+ * Enabling resets the totals and the stage
  * filter of tns_profile_only (call that after enabling). */
 int tns_profile_enable(tns_ctx *ctx, int on);
 /* Restrict the timing to one stage (NULL or "": every stage).  Each timed stage costs two HIP

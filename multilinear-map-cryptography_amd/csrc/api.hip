@@ -1,4 +1,4 @@
-// api.hip -- the device-side C ABI of include/tns.h: device info, contexts, setup and SRS, the KZG /
+// api.hip -- the device-side C ABI of include/tns.h: device info, contexts, setup, SRS and SRS files, the KZG /
 // MSM / interpolation / MLE / sum-check entry points, device buffers, the clock probe and the
 // profiler read-out.  (The provers are in prove.hip, the host-only entry points in abi_host.cpp.)
 #include "abi.hpp"
@@ -300,6 +300,88 @@ int tns_srs_lagrange_download(tns_ctx *ctx, tns_srs *srs, size_t n, uint64_t *g1
     ctx->c.lagrange_commit = saved;
     if (!b) throw Error(TNS_ERR_INVALID_PARAMETERS, "tau is an interpolation node: no Lagrange basis");
     TNS_HIP(hipMemcpy(g1_affine_out, b->points.p, sizeof(G1Affine) * n, hipMemcpyDeviceToHost));
+    return TNS_OK;
+  });
+}
+
+// ---------------------------------------------------------------- SRS files (srs_io.hip)
+size_t tns_srs_serialized_size(size_t n, int compressed) { return g1_vec_serialized_size(n, compressed != 0); }
+
+static void check_whole_srs(const tns_ctx *ctx, const tns_srs *srs) {
+  if (!ctx || !srs) throw Error(TNS_ERR_INVALID_PARAMETERS, "null context or SRS");
+  if (srs->s.first != 0 || srs->s.held < srs->s.n)
+    throw Error(TNS_ERR_INVALID_PARAMETERS, "SRS files hold all of g1_powers (this SRS is a shard)");
+}
+
+// n device points as a Vec<G1Affine> file, under tns_proof_serialize's buffer contract
+static void serialize_points(tns_ctx *ctx, const G1Affine *pts, size_t n, int compressed, uint8_t *out, size_t cap,
+                             size_t *len) {
+  if (!len) throw Error(TNS_ERR_INVALID_PARAMETERS, "null length output");
+  *len = g1_vec_serialized_size(n, compressed != 0);
+  if (!out) return;
+  if (*len > cap) throw Error(TNS_ERR_INVALID_PARAMETERS, "output buffer too small");
+  g1_vec_put_header(n, out);
+  g1_encode_dev(&ctx->c, pts, n, compressed != 0, out + 8);
+}
+
+int tns_srs_serialize(tns_ctx *ctx, const tns_srs *srs, int compressed, uint8_t *out, size_t cap, size_t *len) {
+  return guarded([&]() {
+    check_whole_srs(ctx, srs);
+    CtxScope g(&ctx->c);
+    serialize_points(ctx, srs->s.points.as<G1Affine>(), srs->s.n, compressed, out, cap, len);
+    return TNS_OK;
+  });
+}
+
+int tns_srs_deserialize(tns_ctx *ctx, const uint8_t *in, size_t len, int compressed, tns_srs **out) {
+  return guarded([&]() {
+    if (!ctx || !out) throw Error(TNS_ERR_INVALID_PARAMETERS, "null context or output");
+    const size_t n = g1_vec_header(in, len, compressed != 0);
+    CtxScope g(&ctx->c);
+    tns_srs *s = new tns_srs();
+    s->s.device = ctx->c.device;
+    s->s.n = n;
+    s->s.held = n;
+    try {
+      G1Affine *p = (G1Affine *)s->s.points.ensure(sizeof(G1Affine) * (n ? n : 1));
+      g1_decode_dev(&ctx->c, in + 8, n, compressed != 0, p);
+    } catch (...) {
+      delete s;
+      throw;
+    }
+    *out = s;
+    return TNS_OK;
+  });
+}
+
+int tns_srs_lagrange_serialize(tns_ctx *ctx, tns_srs *srs, size_t n, int compressed, uint8_t *out, size_t cap,
+                               size_t *len) {
+  return guarded([&]() {
+    check_whole_srs(ctx, srs);
+    CtxScope g(&ctx->c);
+    if (!srs->s.has_tau && !srs->s.lagrange.count(std::make_tuple(n, (size_t)0, n)))
+      throw Error(TNS_ERR_INVALID_PARAMETERS, "SRS has no tau (and no basis prepared from its powers)");
+    if (n == 0 || (n & (n - 1))) throw Error(TNS_ERR_INVALID_PARAMETERS, "Lagrange basis size must be a power of two");
+    serialize_points(ctx, nullptr, n, compressed, nullptr, 0, len);  // sizing alone builds nothing
+    if (!out) return TNS_OK;
+    if (*len > cap) throw Error(TNS_ERR_INVALID_PARAMETERS, "output buffer too small");
+    const bool saved = ctx->c.lagrange_commit;
+    ctx->c.lagrange_commit = true;
+    const LagrangeBasis *b = lagrange_basis_dev(&ctx->c, srs->s, n, 0, n);
+    ctx->c.lagrange_commit = saved;
+    if (!b) throw Error(TNS_ERR_INVALID_PARAMETERS, "tau is an interpolation node: no Lagrange basis");
+    serialize_points(ctx, b->points.as<G1Affine>(), n, compressed, out, cap, len);
+    return TNS_OK;
+  });
+}
+
+int tns_srs_lagrange_deserialize(tns_ctx *ctx, tns_srs *srs, const uint8_t *in, size_t len, int compressed,
+                                 const uint8_t seed[32]) {
+  return guarded([&]() {
+    check_whole_srs(ctx, srs);
+    const size_t n = g1_vec_header(in, len, compressed != 0);
+    CtxScope g(&ctx->c);
+    lagrange_basis_attach_dev(&ctx->c, srs->s, in + 8, n, compressed != 0, seed);
     return TNS_OK;
   });
 }

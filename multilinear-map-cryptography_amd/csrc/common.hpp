@@ -662,6 +662,19 @@ const Fr *bary_weights_dev(Ctx *c, size_t N, size_t first, size_t cnt);
 // tfree.hip: the Lagrange basis [L_j(tau)]G, j < N, from g1_powers[0..N) alone (no tau); cached in
 // srs.lagrange under (N, 0, N) like the tau-derived one
 const LagrangeBasis *lagrange_basis_from_powers_dev(Ctx *c, const Srs &srs, size_t N);
+// srs_io.hip: Vec<G1Affine> in ark-serialize form (u64 LE count, then 32 / 64 bytes a point),
+// decoded, validated and encoded on the device.  g1_vec_header returns the count of a file whose
+// length must match it exactly; g1_decode_dev / g1_encode_dev move n points between wire bytes on
+// the host and points on the device (a refused point throws, naming the lowest such index).
+size_t g1_vec_serialized_size(size_t n, bool compressed);
+size_t g1_vec_header(const uint8_t *in, size_t len, bool compressed);
+void g1_vec_put_header(size_t n, uint8_t *out);
+void g1_decode_dev(Ctx *c, const uint8_t *bytes, size_t n, bool compressed, G1Affine *out);
+void g1_encode_dev(Ctx *c, const G1Affine *pts, size_t n, bool compressed, uint8_t *bytes);
+// the stored basis [L_j(tau)]G, j < N (wire bytes), checked against g1_powers[0..N) with scalars
+// from `seed` (nullptr: from the OS) and then cached in srs.lagrange under (N, 0, N)
+void lagrange_basis_attach_dev(Ctx *c, const Srs &srs, const uint8_t *bytes, size_t N, bool compressed,
+                               const uint8_t seed[32]);
 
 // comm.cpp: the exchange steps of a sharded proof
 struct Comm {

@@ -247,6 +247,52 @@ class Srs:
         _check(N.load().tns_srs_lagrange_download(self.ctx.handle, self.handle, n, N.p64(out)))
         return out
 
+    def _serialized(self, call, n: int, compressed: bool) -> bytes:
+        out = np.empty(N.load().tns_srs_serialized_size(n, 1 if compressed else 0), dtype=np.uint8)
+        ln = C.c_size_t()
+        _check(call(N.p8(out), len(out), C.byref(ln)))
+        assert ln.value == len(out)
+        return out.tobytes()
+
+    def serialize(self, compressed: bool = True) -> bytes:
+        """g1_powers as arkworks writes the Vec<G1Affine> (`g1_powers.serialize_compressed`): a u64
+        LE count, then 32 (compressed) or 64 bytes a point; encoded on the device.  Unsharded only."""
+        c = 1 if compressed else 0
+        return self._serialized(lambda p, cap, ln: N.load().tns_srs_serialize(self.ctx.handle, self.handle, c, p, cap, ln),
+                                len(self), compressed)
+
+    @classmethod
+    def deserialize(cls, data: bytes, compressed: bool = True, device: int = 0) -> "Srs":
+        """An SRS without tau from serialize()'s format, every point decoded and validated on the
+        device; a bad point raises InvalidParameters naming its index."""
+        ctx = Context.get(device)
+        h = C.c_void_p()
+        buf = np.frombuffer(data, dtype=np.uint8)
+        _check(N.load().tns_srs_deserialize(ctx.handle, N.p8(buf), len(buf), 1 if compressed else 0, C.byref(h)))
+        return cls(ctx, h)
+
+    def lagrange_serialize(self, n: int, compressed: bool = True) -> bytes:
+        """The Lagrange basis [L_j(tau)]G of the nodes 0..n-1 (built if needed) in serialize()'s format."""
+        c = 1 if compressed else 0
+        return self._serialized(
+            lambda p, cap, ln: N.load().tns_srs_lagrange_serialize(self.ctx.handle, self.handle, n, c, p, cap, ln),
+            n, compressed)
+
+    def lagrange_deserialize(self, data: bytes, compressed: bool = True, seed: Optional[bytes] = None):
+        """Attach a stored Lagrange basis (lagrange_serialize's bytes; the node count is the file's) to
+        this SRS after checking it against g1_powers with random scalars: a tau-less SRS then proves
+        through the Lagrange route without prepare_lagrange_from_powers.  seed: 32 bytes for the
+        check's scalars; None (default) draws them from the OS -- the check only binds a file whose
+        author cannot know the scalars.  A basis that does not match raises InvalidParameters."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        sp = None
+        if seed is not None:
+            if len(seed) != 32:
+                raise InvalidParameters("seed must be 32 bytes")
+            sp = (C.c_uint8 * 32)(*seed)
+        _check(N.load().tns_srs_lagrange_deserialize(self.ctx.handle, self.handle, N.p8(buf), len(buf),
+                                                     1 if compressed else 0, sp))
+
     def download(self, n: Optional[int] = None) -> np.ndarray:
         n = len(self) if n is None else n
         out = np.zeros((n, 8), dtype=np.uint64)
@@ -302,6 +348,16 @@ class CommitmentParams:
         if tau is not None:
             srs.set_tau(tau)
         return cls(srs, tau)
+
+    def serialize_g1_powers(self, compressed: bool = True) -> bytes:
+        """g1_powers in ark-serialize form (`g1_powers.serialize_compressed` / `_uncompressed`)."""
+        return self.srs.serialize(compressed)
+
+    @classmethod
+    def deserialize_g1_powers(cls, data: bytes, compressed: bool = True, device: int = 0) -> "CommitmentParams":
+        """Params without tau from a serialised g1_powers (a ceremony file), validated on the device:
+        like from_g1_limbs without tau."""
+        return cls(Srs.deserialize(data, compressed, device), None)
 
     @classmethod
     def from_g1_powers(cls, g1_powers: Sequence[G1Affine], device: int = 0, tau=None) -> "CommitmentParams":

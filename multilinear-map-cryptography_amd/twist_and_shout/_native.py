@@ -93,6 +93,12 @@ SIGNATURES = [
     ("tns_srs_prepare_lagrange", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("tns_srs_lagrange_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, U64P]),
     ("tns_srs_prepare_lagrange_from_powers", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("tns_srs_serialized_size", C.c_size_t, [C.c_size_t, C.c_int]),
+    ("tns_srs_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, U8P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tns_srs_deserialize", C.c_int, [C.c_void_p, U8P, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    ("tns_srs_lagrange_serialize", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, U8P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tns_srs_lagrange_deserialize", C.c_int, [C.c_void_p, C.c_void_p, U8P, C.c_size_t, C.c_int, U8P]),
     ("tns_ctx_set_commit_basis", C.c_int, [C.c_void_p, C.c_int]),
     ("tns_ctx_set_msm_tables", C.c_int, [C.c_void_p, C.c_int]),
     ("tns_ctx_set_upload_chunks", C.c_int, [C.c_void_p, C.c_int]),
