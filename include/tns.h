@@ -240,6 +240,35 @@ int tns_kzg_open_evals(tns_ctx *ctx, const tns_srs *srs, const uint64_t *evals, 
  * TNS_ERR_COMMITMENT ("Index out of bounds"). */
 int tns_vc_open(tns_ctx *ctx, const tns_srs *srs, const uint64_t *vec, size_t n, size_t index, uint64_t value[4],
                 uint64_t proof_proj[12]);
+/* Every opening of a vector at once -- KZGVectorCommitment::open (src/commitments.rs:435-471) for all
+ * n indices in one O(n log n) pass (three correlations over the Lagrange basis on the group NTT,
+ * vc_open.hip) instead of n calls of one MSM of n points each.  Any n >= 1.
+ * proofs_affine_out: n proofs as affine uint64_t[8] each, identity = all zeros -- tns_srs_download's
+ * encoding, so the result can go to tns_srs_upload or a G1-vector file; proof i is what tns_vc_open
+ * returns for index i.  The values are the vector itself and are not returned.
+ * The pass needs the Lagrange basis of n nodes and uses it whatever tns_ctx_set_commit_basis says
+ * (there is no coefficient route to fall back to): from tau, or prepared / attached beforehand.
+ * Per (SRS, n) it keeps the correlation A of the basis (64 bytes a point) and 64 n + 32 M bytes of
+ * scalars, M = next_pow2(2 n - 1), as long as the SRS lives; tns_srs_prepare_open_all builds them
+ * ahead of the first call (setup, like tns_srs_prepare_lagrange), else the first call does.
+ * Errors: n == 0 -> TNS_ERR_POLYNOMIAL; n > srs_len -> TNS_ERR_COMMITMENT ("Polynomial degree exceeds
+ * setup size"); a sharded SRS, or one that provides no basis of n nodes (no tau, nothing prepared
+ * or attached) -> TNS_ERR_INVALID_PARAMETERS; a failed device allocation -> TNS_ERR_OOM.  Nothing
+ * is written on error. */
+int tns_vc_open_all(tns_ctx *ctx, tns_srs *srs, const uint64_t *vec, size_t n, uint64_t *proofs_affine_out);
+/* Setup for tns_vc_open_all (the batched src/commitments.rs:435-471) at n entries: builds and caches what
+ * the pass keeps per (SRS, n), the Lagrange basis included when tau provides it.  Same errors. */
+int tns_srs_prepare_open_all(tns_ctx *ctx, tns_srs *srs, size_t n);
+/* k openings of one vector (src/commitments.rs:435-471 per index), in request order; duplicates are
+ * allowed, k == 0 returns at once.  values_out: uint64_t[4] each; proofs_proj_out: uint64_t[12]
+ * each, normalised as tns_vc_open returns them.  The vector is uploaded once.  Rule: with
+ * M = next_pow2(2 n - 1), the call takes the all-index pass and gathers from it when
+ * k > 8 log2(M) and the SRS provides the Lagrange basis of n nodes; otherwise it opens index by
+ * index exactly as tns_vc_open does (same routes, same errors).  Either way the same openings.
+ * Any index >= n -> TNS_ERR_COMMITMENT ("Index out of bounds") with no output written; the other
+ * errors are tns_vc_open_all's. */
+int tns_vc_open_many(tns_ctx *ctx, const tns_srs *srs, const uint64_t *vec, size_t n, const uint64_t *indices,
+                     size_t k, uint64_t *values_out, uint64_t *proofs_proj_out);
 /* KZGCommitmentValue::hash (src/commitments.rs:73-84).  Host only. */
 int tns_commitment_hash(const uint64_t proj[12], uint64_t out[4]);
 /* Raw MSM: sum_i scalars[i] * points[i] over the first n SRS points. */
@@ -317,6 +346,11 @@ int tns_twist_prove_device(tns_ctx *ctx, const tns_srs *srs, const tns_params *p
 int tns_shout_prove_device(tns_ctx *ctx, const tns_srs *srs, const tns_params *params,
                            const uint64_t *d_entries, size_t n_entries, const uint64_t *d_indices,
                            size_t n_lookups, tns_proof *out);
+/* tns_vc_open_all (src/commitments.rs:435-471 for every index) on a device-resident vector (n Fr) with
+ * a device-resident output (n affine points, 64 n bytes), e.g. buffers of tns_buffer_upload: no PCIe
+ * in the call. */
+int tns_vc_open_all_device(tns_ctx *ctx, tns_srs *srs, const uint64_t *d_vec, size_t n,
+                           uint64_t *d_proofs_affine_out);
 /* KZGCommitment::commit / MSM on device-resident scalars. */
 int tns_msm_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_scalars, size_t n,
                    uint64_t out_proj[12]);

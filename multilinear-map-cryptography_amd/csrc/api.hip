@@ -260,6 +260,8 @@ int tns_srs_set_tau(tns_srs *srs, const uint64_t tau[4]) {
     }
     for (auto &kv : srs->s.lagrange) delete kv.second;
     srs->s.lagrange.clear();
+    for (auto &kv : srs->s.open_all) delete kv.second;  // (correlations of the bases just dropped)
+    srs->s.open_all.clear();
     srs->s.tau = t;
     srs->s.has_tau = true;
     return TNS_OK;

@@ -195,6 +195,15 @@ struct LagrangeBasis {
   ~LagrangeBasis() { delete fb; }
 };
 
+// What tns_vc_open_all keeps per (SRS, n) (vc_open.hip): the correlation A_i = sum_j Lambda_j / (j - i)
+// of the Lagrange basis, the spectrum of its kernel, and the vector-independent scalars of f'(i).
+struct OpenAllPlan {
+  size_t n = 0, M = 0;  // M = next_pow2(2 n - 1): the cyclic length
+  DevBuf A;             // G1Affine[n]
+  DevBuf spec;          // Fr[M]: fr_ntt of the kernel, scaled by 1 / M (Montgomery, bit-reversed order)
+  DevBuf iw, D;         // Fr[n]: 1 / w_i, and (1 / w_i) sum_j w_j / (i - j)
+};
+
 struct Srs {
   DevBuf points;  // G1Affine[n]
   size_t n = 0;
@@ -207,11 +216,13 @@ struct Srs {
   mutable std::map<std::tuple<size_t, size_t, size_t>, LagrangeBasis *> lagrange;
   size_t first = 0, held = 0;  // points[0..held) are g1_powers[first .. first + held) (sharded SRS)
   mutable FixedBase *fb = nullptr;                        // window table of `points` (lazy)
+  mutable std::map<size_t, OpenAllPlan *> open_all;       // n -> tns_vc_open_all's plan (cache)
   Srs() = default;
   Srs(const Srs &) = delete;
   Srs &operator=(const Srs &) = delete;
   ~Srs() {
     for (auto &kv : lagrange) delete kv.second;
+    for (auto &kv : open_all) delete kv.second;
     delete fb;
   }
 };
@@ -335,6 +346,8 @@ struct Ctx {
   DevBuf prove_ws[12];  // resident trace / evaluation / quotient vectors of Twist/Shout::prove
   DevBuf twiddles;  // omega_{2^k}^i, i < 2^(k-1), natural order, for the largest k seen
   unsigned twiddle_log = 0;
+  DevBuf glv_tw;    // the same table split for the group NTT (glv_twiddles), for the largest k vc_open.hip saw
+  unsigned glv_tw_log = 0;
   std::vector<InterpPlan *> plans;  // indexed by log_n
   std::map<uint32_t, DevBuf *> pass_tw;  // four-step pass twiddles keyed by (lo << 8 | r)
   std::map<std::tuple<size_t, size_t, size_t>, DevBuf *> bary_w;  // (N, first, count) -> weights
@@ -662,6 +675,79 @@ const Fr *bary_weights_dev(Ctx *c, size_t N, size_t first, size_t cnt);
 // tfree.hip: the Lagrange basis [L_j(tau)]G, j < N, from g1_powers[0..N) alone (no tau); cached in
 // srs.lagrange under (N, 0, N) like the tau-derived one
 const LagrangeBasis *lagrange_basis_from_powers_dev(Ctx *c, const Srs &srs, size_t N);
+// tfree.hip's group NTT over G1, shared with vc_open.hip.  X holds N / M transforms of size M, each
+// in place: forward DIF (natural in, bit-reversed out) or inverse DIT (bit-reversed in, natural out,
+// unscaled), a butterfly's twiddle multiplication split by the GLV endomorphism.  TG = glv_twiddles
+// of the ntt_twiddles table TW[0..M) (downloaded, split on host threads, uploaded: synchronises);
+// fr_ntt is the same radix-2 transform on scalars, so spectra of both line up index by index.
+struct GlvScalar {
+  uint32_t k1[4], k2[4];  // magnitudes
+  uint32_t neg;           // bit 0: k1 < 0, bit 1: k2 < 0
+};
+void glv_twiddles(Ctx *c, const Fr *TW, size_t N, DevBuf &out);
+void g_ntt(hipStream_t st, G1Xyzz *X, size_t N, size_t M, const GlvScalar *TG, bool inverse);
+void fr_ntt(hipStream_t st, Fr *X, size_t N, size_t M, const Fr *TW, bool inverse);
+// the kernels that multiply points by scalars: 3 waves per SIMD (168 VGPRs; the default bound let
+// the compiler take 258 registers, one wave per SIMD)
+#define TF_WAVES 3
+// the group NTT's butterflies (GLV joint multiplication: P, phi(P), their sum and the accumulator)
+#ifndef TF_NTT_WAVES
+#define TF_NTT_WAVES 2
+#endif
+
+__device__ __forceinline__ G1Xyzz xyzz_negate(const G1Xyzz &p) {
+  G1Xyzz r = p;
+  r.y = neg(p.y);
+  return r;
+}
+
+// dbl-2008-s-1 in the lazy domain (coordinates in [0, 2M), as xyzz_add_lazy): no final
+// subtractions in the products, Y3 as one reduction of M (S - X3) + Y (2M - W)
+__device__ __forceinline__ G1Xyzz xyzz_dbl_lazy(const G1Xyzz &p) {
+  if (fq_zero_lazy(p.zz) || fq_zero_lazy(p.y)) return G1Xyzz::inf();
+  const Fq U = add2_dev(p.y, p.y);
+  const Fq V = sqr_lazy_dev(U);
+  const Fq W = mul_lazy_dev(U, V);
+  const Fq S = mul_lazy_dev(p.x, V);
+  const Fq X2 = sqr_lazy_dev(p.x);
+  const Fq M = add2_dev(add2_dev(X2, X2), X2);
+  G1Xyzz r;
+  r.x = sub2_dev(sqr_lazy_dev(M), add2_dev(S, S));
+  r.y = mul2_lazy_dev(M, sub2_dev(S, r.x), p.y, const_minus_dev<FqCfg, true>(W));
+  r.zz = mul_lazy_dev(V, p.zz);
+  r.zzz = mul_lazy_dev(W, p.zzz);
+  return r;
+}
+
+// k P for a canonical scalar k: left to right from k's top bit.  Where the lanes of a wave share
+// k (the group NTT maps equal twiddles to one wave), the branches are uniform.
+static __device__ G1Xyzz xyzz_mul_canon(const G1Xyzz &P, const Fr &k) {
+  G1Xyzz acc = G1Xyzz::inf();
+  bool started = false;
+#pragma unroll 1
+  for (int l = 7; l >= 0; l--) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) w = q == l ? k.v[q] : w;  // (a dynamic index would use scratch)
+    if (!started && w == 0) continue;
+#pragma unroll 1
+    for (int b = 31; b >= 0; b--) {
+      if (started) acc = xyzz_dbl_lazy(acc);
+      if ((w >> b) & 1u) {
+        acc = started ? xyzz_add_lazy(acc, P) : P;
+        started = true;
+      }
+    }
+  }
+  return xyzz_canon(acc);
+}
+// vc_open.hip: every opening of a KZG vector commitment in one pass (tns_vc_open_all).  proofs_dev:
+// n affine points on the device; vec_dev: the n entries (Montgomery), only read.  Throws
+// TNS_ERR_INVALID_PARAMETERS when the SRS provides no Lagrange basis of n nodes.
+const OpenAllPlan *open_all_plan_dev(Ctx *c, const Srs &srs, size_t n);
+void vc_open_all_dev(Ctx *c, const Srs &srs, const Fr *vec_dev, size_t n, G1Affine *proofs_dev);
+// whether k openings of a vector of n entries take the all-index pass (tns_vc_open_many's rule)
+bool vc_open_many_takes_all(size_t n, size_t k);
 // srs_io.hip: Vec<G1Affine> in ark-serialize form (u64 LE count, then 32 / 64 bytes a point),
 // decoded, validated and encoded on the device.  g1_vec_header returns the count of a file whose
 // length must match it exactly; g1_decode_dev / g1_encode_dev move n points between wire bytes on

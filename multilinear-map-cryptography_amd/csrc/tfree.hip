@@ -39,60 +39,8 @@ namespace tns {
 namespace {
 
 constexpr size_t TF_DIRECT_H = 4;  // children of <= 4 nodes: direct correlation (h scalar mults / output)
-// the kernels that multiply points by scalars: 3 waves per SIMD (168 VGPRs; the default bound let
-// the compiler take 258 registers, one wave per SIMD)
-#define TF_WAVES 3
-// the group NTT's butterflies (GLV joint multiplication: P, phi(P), their sum and the accumulator)
-#ifndef TF_NTT_WAVES
-#define TF_NTT_WAVES 2
-#endif
-
-__device__ __forceinline__ G1Xyzz xyzz_negate(const G1Xyzz &p) {
-  G1Xyzz r = p;
-  r.y = neg(p.y);
-  return r;
-}
-
-// dbl-2008-s-1 in the lazy domain (coordinates in [0, 2M), as xyzz_add_lazy): no final
-// subtractions in the products, Y3 as one reduction of M (S - X3) + Y (2M - W)
-__device__ __forceinline__ G1Xyzz xyzz_dbl_lazy(const G1Xyzz &p) {
-  if (fq_zero_lazy(p.zz) || fq_zero_lazy(p.y)) return G1Xyzz::inf();
-  const Fq U = add2_dev(p.y, p.y);
-  const Fq V = sqr_lazy_dev(U);
-  const Fq W = mul_lazy_dev(U, V);
-  const Fq S = mul_lazy_dev(p.x, V);
-  const Fq X2 = sqr_lazy_dev(p.x);
-  const Fq M = add2_dev(add2_dev(X2, X2), X2);
-  G1Xyzz r;
-  r.x = sub2_dev(sqr_lazy_dev(M), add2_dev(S, S));
-  r.y = mul2_lazy_dev(M, sub2_dev(S, r.x), p.y, const_minus_dev<FqCfg, true>(W));
-  r.zz = mul_lazy_dev(V, p.zz);
-  r.zzz = mul_lazy_dev(W, p.zzz);
-  return r;
-}
-
-// k P for a canonical scalar k: left to right from k's top bit.  Where the lanes of a wave share
-// k (the group NTT maps equal twiddles to one wave), the branches are uniform.
-__device__ G1Xyzz xyzz_mul_canon(const G1Xyzz &P, const Fr &k) {
-  G1Xyzz acc = G1Xyzz::inf();
-  bool started = false;
-#pragma unroll 1
-  for (int l = 7; l >= 0; l--) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) w = q == l ? k.v[q] : w;  // (a dynamic index would use scratch)
-    if (!started && w == 0) continue;
-#pragma unroll 1
-    for (int b = 31; b >= 0; b--) {
-      if (started) acc = xyzz_dbl_lazy(acc);
-      if ((w >> b) & 1u) {
-        acc = started ? xyzz_add_lazy(acc, P) : P;
-        started = true;
-      }
-    }
-  }
-  return xyzz_canon(acc);
-}
+// (the launch bounds TF_WAVES / TF_NTT_WAVES, the lazy-domain scalar multiplication xyzz_mul_canon and
+// the split twiddle GlvScalar are in common.hpp: vc_open.hip runs the same group NTT)
 
 // ---- GLV: phi(x, y) = (beta x, y) equals lambda (x, y) on G1 (beta a primitive cube root of unity
 // in Fq, lambda the matching one in Fr: phi(G) = lambda G, checked against the C oracle when the
@@ -100,11 +48,7 @@ __device__ G1Xyzz xyzz_mul_canon(const G1Xyzz &P, const Fr &k) {
 // |k1|, |k2| < 2^127: half the doublings of a 254-bit double-and-add.  The group NTT's twiddles are
 // split once per basis build on the host (Babai rounding in the reduced lattice basis
 // (a1, b1), (a2, b2) of {(a, b): a + b lambda = 0 mod r}; g1 = floor(b2 2^256 / r),
-// g2 = floor(-b1 2^256 / r)).
-struct GlvScalar {
-  uint32_t k1[4], k2[4];  // magnitudes
-  uint32_t neg;           // bit 0: k1 < 0, bit 1: k2 < 0
-};
+// g2 = floor(-b1 2^256 / r)).  (GlvScalar: common.hpp)
 // beta in Montgomery form (canonical 0x30644e72e131a0295e6dd9e7e0acccb0c28f069fbb966e3de4bd44e5607cfd48)
 __constant__ uint32_t kGlvBeta[8] = {0x13e80b9cu, 0x3350c88eu, 0xdb5e56b9u, 0x7dce557cu,
                                      0xb615564au, 0x6001b4b8u, 0x020217e0u, 0x2682e617u};
@@ -217,8 +161,10 @@ __global__ void __launch_bounds__(256) k_tf_canon_twiddles(const Fr *__restrict_
     out[i] = from_mont(TW[i]);
 }
 
+}  // namespace
+
 // the twiddle table TW[0..N) split for the group NTT (download, split on host threads, upload)
-static void glv_twiddles(Ctx *c, const Fr *TW, size_t N, DevBuf &out) {
+void glv_twiddles(Ctx *c, const Fr *TW, size_t N, DevBuf &out) {
   DevBuf canon;
   Fr *d_canon = (Fr *)canon.ensure(sizeof(Fr) * N);
   k_tf_canon_twiddles<<<grid_for(N, 256, 4096), 256, 0, c->stream>>>(TW, N, d_canon);
@@ -253,6 +199,8 @@ static void glv_twiddles(Ctx *c, const Fr *TW, size_t N, DevBuf &out) {
   TNS_HIP(hipMemcpyAsync(d, g.data(), sizeof(GlvScalar) * N, hipMemcpyHostToDevice, c->stream));
   TNS_HIP(hipStreamSynchronize(c->stream));
 }
+
+namespace {
 
 // ---- scalar side: the subproduct tree ell_S, monic, leading coefficient implicit.  Level e holds
 // the N / 2^e nodes of size h = 2^e, node k's h coefficients at [k h, (k + 1) h).
@@ -321,7 +269,9 @@ __global__ void __launch_bounds__(256, TF_NTT_WAVES) k_tf_gdit(G1Xyzz *__restric
   }
 }
 
-static void fr_ntt(hipStream_t st, Fr *X, size_t N, size_t M, const Fr *TW, bool inverse) {
+}  // namespace
+
+void fr_ntt(hipStream_t st, Fr *X, size_t N, size_t M, const Fr *TW, bool inverse) {
   const unsigned g = grid_for(N / 2, 256, 1u << 20);
   if (!inverse) {
     for (size_t hs = M / 2; hs >= 1; hs /= 2) k_tf_fdif<<<g, 256, 0, st>>>(X, N, hs, TW);
@@ -330,6 +280,8 @@ static void fr_ntt(hipStream_t st, Fr *X, size_t N, size_t M, const Fr *TW, bool
   }
   TNS_LAUNCH_CHECK();
 }
+
+namespace {
 
 // a -> A (padded to 2h), b -> B, per parent
 __global__ void __launch_bounds__(256) k_tf_pad2(const Fr *__restrict__ Lin, size_t N, size_t h, Fr *__restrict__ A,
@@ -413,7 +365,9 @@ __global__ void __launch_bounds__(256) k_tf_take(const G1Xyzz *__restrict__ Yl, 
   }
 }
 
-static void g_ntt(hipStream_t st, G1Xyzz *X, size_t N, size_t M, const GlvScalar *TG, bool inverse) {
+}  // namespace
+
+void g_ntt(hipStream_t st, G1Xyzz *X, size_t N, size_t M, const GlvScalar *TG, bool inverse) {
   const unsigned g = grid_for(N / 2, 256, 1u << 20);
   if (!inverse) {
     for (size_t hs = M / 2; hs >= 1; hs /= 2) k_tf_gdif<<<g, 256, 0, st>>>(X, N, hs, TG);
@@ -422,6 +376,8 @@ static void g_ntt(hipStream_t st, G1Xyzz *X, size_t N, size_t M, const GlvScalar
   }
   TNS_LAUNCH_CHECK();
 }
+
+namespace {
 
 __global__ void __launch_bounds__(256) k_tf_from_affine(const G1Affine *__restrict__ g, size_t N,
                                                         G1Xyzz *__restrict__ H) {

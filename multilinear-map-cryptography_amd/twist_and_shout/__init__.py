@@ -241,6 +241,11 @@ class Srs:
         the Lagrange route."""
         _check(N.load().tns_srs_prepare_lagrange_from_powers(self.ctx.handle, self.handle, n))
 
+    def prepare_open_all(self, n: int):
+        """Build what KZGVectorCommitment.open_all keeps per (SRS, n) now (setup time) instead of at the
+        first call of that size (tns_srs_prepare_open_all); any n >= 1."""
+        _check(N.load().tns_srs_prepare_open_all(self.ctx.handle, self.handle, n))
+
     def lagrange_points(self, n: int) -> np.ndarray:
         """The Lagrange basis [L_j(tau)]G of the nodes 0..n-1 (affine limbs, host copy)."""
         out = np.zeros((n, 8), dtype=np.uint64)
@@ -649,6 +654,31 @@ class KZGVectorCommitment:
         _check(N.load().tns_vc_open(params.srs.ctx.handle, params.srs.handle, N.p64(_nonempty(y)), len(y), index,
                                     N.p64(v), N.p64(pi)))
         return from_mont(v)[0], KZGProof(_g1_from_proj(pi))
+
+    @staticmethod
+    def open_all(params: CommitmentParams, vector) -> np.ndarray:
+        """The proofs of open(params, vector, i) for every i in one O(n log n) pass (tns_vc_open_all):
+        an (n, 8) uint64 array of affine Montgomery limbs, identity = zeros -- Srs.download()'s form,
+        so CommitmentParams.from_g1_limbs takes it.  Needs the Lagrange basis of n nodes."""
+        y = _as_mont(vector)
+        out = np.zeros((len(y), 8), dtype=np.uint64)
+        _check(N.load().tns_vc_open_all(params.srs.ctx.handle, params.srs.handle, N.p64(_nonempty(y)), len(y),
+                                        N.p64(out if len(y) else np.zeros((1, 8), dtype=np.uint64))))
+        return out
+
+    @staticmethod
+    def open_many(params: CommitmentParams, vector, indices) -> List[Tuple[int, KZGProof]]:
+        """open(params, vector, i) for each i of indices, in that order (duplicates allowed), with the
+        vector uploaded once; many indices take the all-index pass (tns_vc_open_many documents the rule)."""
+        y = _as_mont(vector)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = len(idx)
+        v = np.zeros((max(k, 1), 4), dtype=np.uint64)
+        pi = np.zeros((max(k, 1), 12), dtype=np.uint64)
+        _check(N.load().tns_vc_open_many(params.srs.ctx.handle, params.srs.handle, N.p64(_nonempty(y)), len(y),
+                                         N.p64(idx if k else np.zeros(1, dtype=np.uint64)), k, N.p64(v), N.p64(pi)))
+        vals = from_mont(v[:k])
+        return [(vals[t], KZGProof(_g1_from_proj(pi[t]))) for t in range(k)]
 
     @staticmethod
     def verify(vk: "CommitmentVerificationKey", commitment: KZGCommitmentValue, index: int, value: int,
@@ -1283,6 +1313,12 @@ def msm_resident(params: CommitmentParams, scalars: DeviceBuffer, n: int) -> np.
     out = np.zeros(12, dtype=np.uint64)
     _check(N.load().tns_msm_device(params.srs.ctx.handle, params.srs.handle, scalars.ptr, n, N.p64(out)))
     return out
+
+
+def vc_open_all_resident(params: CommitmentParams, vector: DeviceBuffer, n: int, proofs: DeviceBuffer):
+    """KZGVectorCommitment.open_all on a vector resident in HBM (n Fr, Montgomery) into a resident
+    output of n affine points (64 n bytes; buffer_download reads it): tns_vc_open_all_device."""
+    _check(N.load().tns_vc_open_all_device(params.srs.ctx.handle, params.srs.handle, vector.ptr, n, proofs.ptr))
 
 
 # ----------------------------------------------------------------------------- one proof across GPUs
