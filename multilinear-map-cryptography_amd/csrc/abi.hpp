@@ -7,7 +7,10 @@
 #include <string>
 #include <vector>
 
-#include "common.hpp"
+#include "comm.hpp"
+#include "ctx.hpp"
+#include "host.hpp"
+#include "srs.hpp"
 
 struct tns_ctx {
   tns::Ctx c;

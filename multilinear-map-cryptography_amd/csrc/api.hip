@@ -6,9 +6,6 @@
 namespace tns {
 
 Ctx::~Ctx() {
-  for (auto *p : plans) delete p;
-  for (auto &kv : pass_tw) delete kv.second;
-  for (auto &kv : bary_w) delete kv.second;
   if (lanes[1].stream) (void)hipStreamDestroy(lanes[1].stream);
   if (side) (void)hipStreamDestroy(side);
   if (copy) (void)hipStreamDestroy(copy);
@@ -258,10 +255,8 @@ int tns_srs_set_tau(tns_srs *srs, const uint64_t tau[4]) {
       if (!(held.x == want.x) || !(held.y == want.y))
         throw Error(TNS_ERR_INVALID_PARAMETERS, "tau does not match the SRS (g1_powers[e] != tau^e * G1)");
     }
-    for (auto &kv : srs->s.lagrange) delete kv.second;
     srs->s.lagrange.clear();
-    for (auto &kv : srs->s.open_all) delete kv.second;  // (correlations of the bases just dropped)
-    srs->s.open_all.clear();
+    srs->s.open_all.clear();  // (correlations of the bases just dropped)
     srs->s.tau = t;
     srs->s.has_tau = true;
     return TNS_OK;

@@ -26,7 +26,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "common.hpp"
+#include "ctx.hpp"
 
 namespace tns {
 
@@ -888,10 +888,10 @@ void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, int c, int W,
   J.E = E;
   J.bucket_bits = bucket_bits;
   uint32_t **K = J.K, **V = J.V;
-  K[0] = (uint32_t *)ln.ws[0].ensure(sizeof(uint32_t) * E);
-  K[1] = (uint32_t *)ln.ws[2].ensure(sizeof(uint32_t) * E);
-  V[0] = (uint32_t *)ln.ws[1].ensure(sizeof(uint32_t) * E);
-  V[1] = (uint32_t *)ln.ws[3].ensure(sizeof(uint32_t) * E);
+  K[0] = (uint32_t *)ln.sort.keys[0].ensure(sizeof(uint32_t) * E);
+  K[1] = (uint32_t *)ln.sort.keys[1].ensure(sizeof(uint32_t) * E);
+  V[0] = (uint32_t *)ln.sort.vals[0].ensure(sizeof(uint32_t) * E);
+  V[1] = (uint32_t *)ln.sort.vals[1].ensure(sizeof(uint32_t) * E);
   DigitArgs A{in.fr, n, 0, c, W, 0, shared, stride, in.mont, in.u64, in.n_u64};
   if (shared)
     while ((1 << A.wb) < W) A.wb++;
@@ -945,21 +945,21 @@ void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, int c, int W,
     throw Error(TNS_ERR_DEVICE, "bucket sort: pass-1 geometry mismatch");
   const size_t max_seg = (size_t)1 << keybits;
   uint32_t **seg = J.seg;
-  seg[0] = (uint32_t *)ln.ws[10].ensure(sizeof(uint32_t) * (max_seg + 1));
-  seg[1] = (uint32_t *)ln.ws[11].ensure(sizeof(uint32_t) * (max_seg + 1));
+  seg[0] = (uint32_t *)ln.sort.seg[0].ensure(sizeof(uint32_t) * (max_seg + 1));
+  seg[1] = (uint32_t *)ln.sort.seg[1].ensure(sizeof(uint32_t) * (max_seg + 1));
   const size_t tmin = 4096;  // the smallest pass tile
   const size_t max_tiles = (E + tmin - 1) / tmin + (max_seg >> bits[npass - 1]) + 1;
   const size_t cnt_len = std::max((size_t)nb * T1, (size_t)BS_MAXBINS * max_tiles) + 1;
   const bool pre = in.precounted && ct && in.pre_shared == shared && in.pre_c == c && in.pre_W == W &&
-                   ln.ws[12].p == in.precounted && ln.ws[12].bytes >= sizeof(uint32_t) * cnt_len;
-  uint32_t *counts = J.counts = (uint32_t *)ln.ws[12].ensure(sizeof(uint32_t) * cnt_len);
-  uint32_t *offs = J.offs = (uint32_t *)ln.ws[13].ensure(sizeof(uint32_t) * cnt_len);
+                   ln.sort.counts.p == in.precounted && ln.sort.counts.bytes >= sizeof(uint32_t) * cnt_len;
+  uint32_t *counts = J.counts = (uint32_t *)ln.sort.counts.ensure(sizeof(uint32_t) * cnt_len);
+  uint32_t *offs = J.offs = (uint32_t *)ln.sort.offs.ensure(sizeof(uint32_t) * cnt_len);
   if (!pre) {  // (precounted: quotient2_count_dev wrote them)
     if (ct) ct->count<<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, counts, nullptr, nullptr);
     else k_bs_count1<<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, counts);
     TNS_LAUNCH_CHECK();
   }
-  exclusive_scan(st, ln.ws[9], counts, offs, (size_t)nb * T1 + 1);
+  exclusive_scan(st, ln.sort.scan, counts, offs, (size_t)nb * T1 + 1);
   const int kf1 = npass > 1 ? J.kf[0] : KF_U32;
   if (ct) ct->scatter<<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, offs, kf1, K[0], V[0]);
   else k_bs_scatter1<BS_TILE><<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, offs, kf1, K[0], V[0]);
@@ -969,10 +969,10 @@ void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, int c, int W,
 
   J.S = nb;
   J.cur = 0;
-  J.tcount = (uint32_t *)ln.ws[14].ensure(sizeof(uint32_t) * 2 * (max_seg + 1));
+  J.tcount = (uint32_t *)ln.sort.tiles.ensure(sizeof(uint32_t) * 2 * (max_seg + 1));
   J.tbase = J.tcount + (max_seg + 1);
-  J.desc = (uint32_t *)ln.ws[15].ensure(sizeof(uint32_t) * max_tiles);
-  J.mcount = (uint32_t *)ln.ws[17].ensure(sizeof(uint32_t) * 2 * (max_seg + 1));
+  J.desc = (uint32_t *)ln.sort.desc.ensure(sizeof(uint32_t) * max_tiles);
+  J.mcount = (uint32_t *)ln.sort.mtiles.ensure(sizeof(uint32_t) * 2 * (max_seg + 1));
   J.mbase = J.mcount + (max_seg + 1);
   J.npass = npass;
   J.shift = shift;
@@ -1017,9 +1017,9 @@ void bucket_sort_passes(BucketSortJob &J) {
     k_bs_tiles<<<grid_for(J.S + 1, 256), 256, 0, st>>>(seg[J.cur], J.S, (uint32_t)tile, J.tcount,
                                                          J.last ? J.mcount : nullptr);
     TNS_LAUNCH_CHECK();
-    exclusive_scan(st, ln.ws[9], J.tcount, J.tbase, J.S + 1);
+    exclusive_scan(st, ln.sort.scan, J.tcount, J.tbase, J.S + 1);
     if (J.last) {  // the readback; pass_rest runs after bucket_sort_finish's wait
-      exclusive_scan(st, ln.ws[9], J.mcount, J.mbase, J.S + 1);
+      exclusive_scan(st, ln.sort.scan, J.mcount, J.mbase, J.S + 1);
       // (with the entry count k_bs_segs1 wrote: the accumulation sizes its chunks from it)
       const void *src[3] = {J.tbase + J.S, J.mbase + J.S, J.valid};
       const size_t by[3] = {4, 4, 4};
@@ -1064,7 +1064,7 @@ void bucket_sort_pass_rest(BucketSortJob &J, bool readback) {
     if (tile == 4096) k_bs_count<4096><<<(unsigned)tiles_bound, BS_BLOCK, 0, st>>>(G, S, tiles_bound, J.K[cur], counts);
     else k_bs_count<BS_TILE><<<(unsigned)tiles_bound, BS_BLOCK, 0, st>>>(G, S, tiles_bound, J.K[cur], counts);
     TNS_LAUNCH_CHECK();
-    exclusive_scan(st, ln.ws[9], counts, offs, scan_len);
+    exclusive_scan(st, ln.sort.scan, counts, offs, scan_len);
   }
   {
     auto *kern = tile == 4096 ? (pk == 0   ? k_bs_scatter<4096, 0>
@@ -1147,7 +1147,7 @@ bool quotient2_count_dev(Ctx *c, const Fr *y0, const Fr *y1, size_t n, const Fr 
   const Pass1Geom g = pass1_geom(n, cw, W, true, cw - 1);
   if (!g.ct || g.npass < 2) return false;
   uint32_t *cnt[2];
-  for (int k = 0; k < 2; k++) cnt[k] = (uint32_t *)c->lanes[k].ws[12].ensure(sizeof(uint32_t) * g.cnt_len);
+  for (int k = 0; k < 2; k++) cnt[k] = (uint32_t *)c->lanes[k].sort.counts.ensure(sizeof(uint32_t) * g.cnt_len);
   TNS_PROF(c, "open_scan", 32.0 * 5 * n);
   TNS_HIP(hipMemsetAsync(bits, 0, 2 * sizeof(unsigned), c->stream));
   k_quotient2_count1<22, 12><<<(unsigned)g.T1, BS_BLOCK, 0, c->stream>>>(y0, y1, v0, v1, n, inv, q0, q1, bits, g.spb, g.wb,
@@ -1162,8 +1162,8 @@ bool bucket_sort_precount_bits(MsmLane &ln, const Fr *scalars, size_t n, int c, 
                                unsigned *bits, SortInput &in, bool want_low64) {
   const Pass1Geom g = pass1_geom(n, c, W, shared, bucket_bits);
   if (!g.ct) return false;
-  uint32_t *counts = (uint32_t *)ln.ws[12].ensure(sizeof(uint32_t) * g.cnt_len);
-  uint64_t *low = want_low64 ? (uint64_t *)ln.ws[18].ensure(sizeof(uint64_t) * n) : nullptr;
+  uint32_t *counts = (uint32_t *)ln.sort.counts.ensure(sizeof(uint32_t) * g.cnt_len);
+  uint64_t *low = want_low64 ? (uint64_t *)ln.sort.low64.ensure(sizeof(uint64_t) * n) : nullptr;
   DigitArgs A{scalars, n, g.spb, c, W, g.wb, shared, 0u, true, nullptr, 0};
   g.ct->count<<<(unsigned)g.T1, BS_BLOCK, 0, ln.stream>>>(A, g.shift, g.nb, g.T1, counts, bits, low);
   TNS_LAUNCH_CHECK();

@@ -19,7 +19,8 @@
 #include <thread>
 #include <vector>
 
-#include "common.hpp"
+#include "comm.hpp"
+#include "ctx.hpp"
 
 namespace tns {
 

@@ -75,14 +75,15 @@ __global__ void k_chunk_prod_final(const Fr *__restrict__ in, size_t n, const Fr
     out[i] = p;
   }
 }
-static void prefix_product(Ctx *c, const Fr *in, size_t n, Fr *out, std::vector<DevBuf *> &tmp, int depth = 0) {
+static void prefix_product(Ctx *c, const Fr *in, size_t n, Fr *out, std::vector<std::unique_ptr<DevBuf>> &tmp,
+                           int depth = 0) {
   size_t C = (n + PROD_K - 1) / PROD_K;
   if (C <= 1) {
     k_chunk_prod_final<<<1, 64, 0, c->stream>>>(in, n, nullptr, out, 1);
     TNS_LAUNCH_CHECK();
     return;
   }
-  if ((int)tmp.size() <= depth) tmp.push_back(new DevBuf());
+  if ((int)tmp.size() <= depth) tmp.push_back(std::make_unique<DevBuf>());
   Fr *P = (Fr *)tmp[depth]->ensure(sizeof(Fr) * 2 * C);
   Fr *S = P + C;
   k_chunk_prod<<<grid_for(C, 256, 1u << 30), 256, 0, c->stream>>>(in, n, P, C);
@@ -225,13 +226,12 @@ void factorial_tables_dev(Ctx *c, size_t nf, Fr *fact, Fr *ifact) {
   Fr *io = (Fr *)iota.ensure(sizeof(Fr) * nf);
   k_iota_fr<<<grid_for(nf, 256), 256, 0, st>>>(io, nf);
   TNS_LAUNCH_CHECK();
-  std::vector<DevBuf *> tmp;
+  std::vector<std::unique_ptr<DevBuf>> tmp;
   prefix_product(c, io, nf, fact, tmp);
   Fr *pr = (Fr *)pre.ensure(sizeof(Fr) * nf);
   k_batch_inverse<<<grid_for((nf + 31) / 32, 256, 1u << 30), 256, 0, st>>>(fact, nf, pr, ifact);
   TNS_LAUNCH_CHECK();
   TNS_HIP(hipStreamSynchronize(st));
-  for (auto *b : tmp) delete b;
 }
 
 static Fr fr_inv_pow2(unsigned s) { return inv(from_u64<FrCfg>((uint64_t)1 << s)); }
@@ -247,11 +247,11 @@ static void make_conv_operand(Ctx *c, const Fr *coeffs, size_t len, unsigned s, 
 }
 
 static InterpPlan *get_plan(Ctx *c, unsigned log_n) {
-  if (c->plans.size() <= log_n) c->plans.resize(log_n + 1, nullptr);
-  if (c->plans[log_n]) return c->plans[log_n];
+  if (c->plans.size() <= log_n) c->plans.resize(log_n + 1);
+  if (c->plans[log_n]) return c->plans[log_n].get();
   const size_t N = (size_t)1 << log_n;
   const size_t NF = N < 4 ? 4 : N;  // factorial table length (>= m + 1 for every level)
-  InterpPlan *P = new InterpPlan();
+  auto P = std::make_unique<InterpPlan>();
   P->log_n = log_n;
   ntt_twiddles(c, log_n + 2);
   hipStream_t st = c->stream;
@@ -322,8 +322,7 @@ static InterpPlan *get_plan(Ctx *c, unsigned log_n) {
     }
     TNS_HIP(hipStreamSynchronize(st));
   }
-  c->plans[log_n] = P;
-  return P;
+  return (c->plans[log_n] = std::move(P)).get();
 }
 
 // ---------------------------------------------------------------- entry point
@@ -340,7 +339,7 @@ void interpolate_consecutive_dev(Ctx *c, const Fr *y, size_t n, Fr *coeffs) {
   }
   InterpPlan *P = get_plan(c, log_n);
   const Fr *fact = P->fact.as<Fr>(), *ifact = P->inv_fact.as<Fr>();
-  Fr *X2 = (Fr *)c->scratch[6].ensure(sizeof(Fr) * 2 * n);
+  Fr *X2 = (Fr *)c->interp_x2.ensure(sizeof(Fr) * 2 * n);
   Fr *A = coeffs;
   // 1. Newton coefficients: first n entries of conv(y_j / j!, (-1)^t / t!)
   {

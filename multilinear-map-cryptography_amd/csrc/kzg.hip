@@ -32,7 +32,7 @@ G1Affine commit_evals(Ctx *c, const Srs &srs, EvalPoly &p, Comm &m) {
   if (p.N > srs.n) throw Error(TNS_ERR_COMMITMENT, "Polynomial degree exceeds setup size");
   p.basis = lagrange_basis_dev(c, srs, p.N, p.first, p.cnt);
   if (p.basis) {
-    const G1Xyzz part = msm_dev(c, p.basis->points.as<G1Affine>(), p.y, p.cnt, p.basis->fb);
+    const G1Xyzz part = msm_dev(c, p.basis->points.as<G1Affine>(), p.y, p.cnt, p.basis->fb.get());
     return xyzz_to_affine(allgather_sum_g1(c, m, part, "commitment partial MSM"));
   }
   if (m.size > 1) throw Error(TNS_ERR_INVALID_PARAMETERS, "sharded proving needs an SRS with tau (Lagrange basis)");
@@ -50,7 +50,7 @@ void open_evals(Ctx *c, const Srs &srs, EvalPoly &p, const Fr &z, Fr *value, G1A
     Fr *q = (Fr *)sbuf.ensure(sizeof(Fr) * p.N);
     TNS_HIP(hipMemcpyAsync(value, p.y + j0, sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
     lagrange_node_quotient_dev(c, p.y, p.N, j0, q);  // synchronises
-    *proof = xyzz_to_affine(msm_dev(c, p.basis->points.as<G1Affine>(), q, p.N, p.basis->fb));
+    *proof = xyzz_to_affine(msm_dev(c, p.basis->points.as<G1Affine>(), q, p.N, p.basis->fb.get()));
     return;
   }
   if (p.basis && !fr_is_node(z, p.N)) {
@@ -70,7 +70,7 @@ void open_evals(Ctx *c, const Srs &srs, EvalPoly &p, const Fr &z, Fr *value, G1A
     }
     *value = mul(ell, S);  // P(z) = ell(z) sum_j w_j y_j / (z - j)
     lagrange_quotient_finish_dev(c, p.y, p.cnt, *value, q);
-    const G1Xyzz pp = msm_dev(c, p.basis->points.as<G1Affine>(), q, p.cnt, p.basis->fb);
+    const G1Xyzz pp = msm_dev(c, p.basis->points.as<G1Affine>(), q, p.cnt, p.basis->fb.get());
     *proof = xyzz_to_affine(allgather_sum_g1(c, m, pp, "opening partial MSM"));
     return;
   }
@@ -136,7 +136,7 @@ void commit_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, Comm 
     return;
   }
   auto args = [](const EvalPoly &p, const ScalarSource *s) {
-    MsmArgs a{p.basis->points.as<G1Affine>(), p.y, p.cnt, p.basis->fb};
+    MsmArgs a{p.basis->points.as<G1Affine>(), p.y, p.cnt, p.basis->fb.get()};
     if (s) a.src = *s;
     return a;
   };
@@ -191,7 +191,7 @@ void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const F
   unsigned *qbits = canon_q ? (unsigned *)c->qbits.ensure(2 * sizeof(unsigned)) : nullptr;
   // the shared-table plan both opening MSMs will take (full-width quotients): the quotient kernel
   // also counts pass 1 of both bucket sorts (their count kernels and one read of q0 / q1 go)
-  const FixedBase *f0 = p0.basis->fb, *f1 = p1.basis->fb;
+  const FixedBase *f0 = p0.basis->fb.get(), *f1 = p1.basis->fb.get();
   const uint32_t *pre[2] = {nullptr, nullptr};
   bool fused = false;
   if (same_nodes && canon_inv && c->msm_tables && f0 && f1 && f0->c == f1->c && f0->W == f1->W)
@@ -204,8 +204,8 @@ void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const F
     lagrange_quotient_finish_dev(c, p1.y, p1.cnt, value[1], q1);
   }
   G1Xyzz pp[2];
-  MsmArgs a0{p0.basis->points.as<G1Affine>(), q0, p0.cnt, p0.basis->fb};
-  MsmArgs a1{p1.basis->points.as<G1Affine>(), q1, p1.cnt, p1.basis->fb};
+  MsmArgs a0{p0.basis->points.as<G1Affine>(), q0, p0.cnt, p0.basis->fb.get()};
+  MsmArgs a1{p1.basis->points.as<G1Affine>(), q1, p1.cnt, p1.basis->fb.get()};
   a0.src.canon_bits = qbits;
   a1.src.canon_bits = qbits ? qbits + 1 : nullptr;
   if (fused) {  // (lane 0 sorts a0, lane 1 a1: neither is late)

@@ -28,7 +28,8 @@
 #include <tuple>
 #include <vector>
 
-#include "common.hpp"
+#include "ctx.hpp"
+#include "srs.hpp"
 #include "hostfield.hpp"
 
 namespace tns {
@@ -382,16 +383,16 @@ __global__ void __launch_bounds__(1024) k_sum_reduce(const Fr *__restrict__ in, 
 static const Fr *bary_weights(Ctx *c, size_t N, size_t first, size_t cnt) {
   const auto key = std::make_tuple(N, first, cnt);
   auto it = c->bary_w.find(key);
-  if (it != c->bary_w.end()) return it->second->as<Fr>();
+  if (it != c->bary_w.end()) return it->second.as<Fr>();
   DevBuf fact, ifact;
   Fr *f = (Fr *)fact.ensure(sizeof(Fr) * N), *fi = (Fr *)ifact.ensure(sizeof(Fr) * N);
   factorial_tables_dev(c, N, f, fi);
-  DevBuf *b = new DevBuf();
-  Fr *w = (Fr *)b->ensure(sizeof(Fr) * cnt);
+  DevBuf b;
+  Fr *w = (Fr *)b.ensure(sizeof(Fr) * cnt);
   k_bary_weights<<<grid_for(cnt, 256), 256, 0, c->stream>>>(fi, N, first, cnt, w);
   TNS_LAUNCH_CHECK();
   TNS_HIP(hipStreamSynchronize(c->stream));  // fact/ifact die here
-  c->bary_w[key] = b;
+  c->bary_w.emplace(key, std::move(b));
   return w;
 }
 
@@ -422,7 +423,7 @@ static NodeSweep node_sweep_begin(Ctx *c, const Fr &xs, size_t n, Fr *pre, size_
   NodeSweep s;
   s.T = chain_count(n);
   s.Tm = from_u64<FrCfg>((uint64_t)s.T);
-  Fr *ws = (Fr *)c->scratch[5].ensure(sizeof(Fr) * (4 * s.T + 4 + 256));
+  Fr *ws = (Fr *)c->scratch.sweep_chains().ensure(sizeof(Fr) * (4 * s.T + 4 + 256));
   s.cp = ws;
   s.sp = ws + s.T;  // 2T: room for two vectors' partial sums
   s.dev = ws + 3 * s.T;
@@ -433,7 +434,7 @@ static NodeSweep node_sweep_begin(Ctx *c, const Fr &xs, size_t n, Fr *pre, size_
   s.inverted = true;
   s.icp = s.dev + 4 + 256;
   const unsigned nb = grid_for(s.T, 256, 1u << 30);
-  Fr *tot = (Fr *)c->scratch[6].ensure(sizeof(Fr) * 2 * nb), *oth = tot + nb;
+  Fr *tot = (Fr *)c->sweep_totals.ensure(sizeof(Fr) * 2 * nb), *oth = tot + nb;
   if (nb > 1024) {  // (more than 2^18 chains: one inverse per block, on the device)
     k_chain_inv<<<nb, 256, 0, c->stream>>>(s.cp, s.T, s.icp, scale);
     TNS_LAUNCH_CHECK();
@@ -474,7 +475,7 @@ const LagrangeBasis *lagrange_basis_dev(Ctx *c, const Srs &srs, size_t N, size_t
   if (first + cnt > N || cnt == 0) throw Error(TNS_ERR_INVALID_PARAMETERS, "node slice outside 0..N-1");
   const auto key = std::make_tuple(N, first, cnt);
   auto it = srs.lagrange.find(key);
-  if (it != srs.lagrange.end()) return it->second;  // also a basis built from g1_powers alone (tfree.hip)
+  if (it != srs.lagrange.end()) return it->second.get();  // also a basis built from g1_powers alone (tfree.hip)
   if (!srs.has_tau || fr_is_node(srs.tau, N)) return nullptr;
   const Fr *w = bary_weights(c, N, first, cnt);
   // ell(tau) over all N nodes
@@ -494,17 +495,11 @@ const LagrangeBasis *lagrange_basis_dev(Ctx *c, const Srs &srs, size_t N, size_t
                                                                            sc, s.icp, s.inverted, w, nullptr, ecp + TG, sc,
                                                                            nullptr);
   TNS_LAUNCH_CHECK();
-  LagrangeBasis *b = new LagrangeBasis();
-  try {
-    G1Affine *pts = (G1Affine *)b->points.ensure(sizeof(G1Affine) * cnt);
-    fixed_base_mul_dev(c, sc, cnt, pts);  // synchronises
-    if (cnt >= ((size_t)1 << 12)) b->fb = fixed_base_try_build(c, pts, cnt);
-  } catch (...) {
-    delete b;
-    throw;
-  }
-  srs.lagrange[key] = b;
-  return b;
+  auto b = std::make_unique<LagrangeBasis>();
+  G1Affine *pts = (G1Affine *)b->points.ensure(sizeof(G1Affine) * cnt);
+  fixed_base_mul_dev(c, sc, cnt, pts);  // synchronises
+  if (cnt >= ((size_t)1 << 12)) b->fb = fixed_base_try_build(c, pts, cnt);
+  return (srs.lagrange[key] = std::move(b)).get();
 }
 
 void lagrange_open_partial_dev(Ctx *c, const Fr *y, size_t N, size_t first, size_t cnt, const Fr &z, Fr *inv,

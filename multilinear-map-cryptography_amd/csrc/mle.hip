@@ -15,7 +15,8 @@
 
 #include <cstring>
 
-#include "common.hpp"
+#include "ctx.hpp"
+#include "host.hpp"
 #include "hostfield.hpp"
 
 namespace tns {
@@ -195,8 +196,8 @@ Fr mle_evaluate_dev(Ctx *c, const Fr *evals, unsigned nv, const Fr *point_host) 
     return r;
   }
   size_t n = (size_t)1 << nv;
-  Fr *a = (Fr *)c->scratch[0].ensure(sizeof(Fr) * (n / 2));
-  Fr *b = (Fr *)c->scratch[1].ensure(sizeof(Fr) * (n / 4 > 0 ? n / 4 : 1));
+  Fr *a = (Fr *)c->scratch.mle_ping().ensure(sizeof(Fr) * (n / 2));
+  Fr *b = (Fr *)c->scratch.mle_pong().ensure(sizeof(Fr) * (n / 4 > 0 ? n / 4 : 1));
   const Fr *src = evals;
   Fr *dst = a;
   for (unsigned j = 0; j < nv; j++) {
@@ -828,10 +829,10 @@ void sumcheck_zero_folds_async(Ctx *c, hipStream_t st, Fr *const *tables, int k,
   const size_t n = (size_t)1 << nv;
   Fr *bufB[MAX_SC_TABLES], *bufC[MAX_SC_TABLES];
   for (int i = 0; i < k; i++) {
-    bufB[i] = (Fr *)c->sc_half[i].ensure(sizeof(Fr) * (n / 2 + 1));
-    bufC[i] = (Fr *)c->sc_pong[i].ensure(sizeof(Fr) * (n / 4 + 1));
+    bufB[i] = (Fr *)c->sc.half[i].ensure(sizeof(Fr) * (n / 2 + 1));
+    bufC[i] = (Fr *)c->sc.pong[i].ensure(sizeof(Fr) * (n / 4 + 1));
   }
-  Fr *d_ch = (Fr *)c->sc_chal.ensure(sizeof(Fr) * nv);
+  Fr *d_ch = (Fr *)c->sc.chal.ensure(sizeof(Fr) * nv);
   TNS_HIP(hipMemcpyAsync(d_ch, chal_pinned, sizeof(Fr) * nv, hipMemcpyHostToDevice, st));
   // rounds 1 .. tail_rnd - 1 fold by r_{rnd-1} in k_sc_fold; the rest (tables of <= 2^12) in
   // one k_sc_fold_tail workgroup, down to one value per table
@@ -891,7 +892,7 @@ void sumcheck_zero_folds_async(Ctx *c, hipStream_t st, Fr *const *tables, int k,
 // last workgroup writes it); a flag that does not arrive within 30 s falls back to a stream
 // synchronize, which reports any device error, and then fails.
 static const ScResult &sc_wait(Ctx *c, uint32_t seq) {
-  volatile ScResult *res = (volatile ScResult *)c->sc_mapped.p;
+  volatile ScResult *res = (volatile ScResult *)c->sc.mapped.p;
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spin = 0; __atomic_load_n(&res->flag, __ATOMIC_ACQUIRE) != seq; spin++) {
     if (const uint32_t w = __atomic_load_n(&res->wait_expired, __ATOMIC_RELAXED)) {
@@ -906,7 +907,7 @@ static const ScResult &sc_wait(Ctx *c, uint32_t seq) {
       throw Error(TNS_ERR_DEVICE, "sum-check round kernel did not publish its sums");
     }
   }
-  return *(const ScResult *)c->sc_mapped.p;
+  return *(const ScResult *)c->sc.mapped.p;
 }
 
 struct ScRun {
@@ -930,22 +931,22 @@ static ScRun sc_run(Ctx *c, int k, const SumcheckTerm *terms, int n_terms, size_
   R.k = k;
   R.q = sc_poly(terms, n_terms, k, R.perm);
   R.max_grid = (unsigned)std::max(1, c->num_cu) * 4;  // one round of resident blocks: threads loop over s
-  ScPoly *qd = (ScPoly *)c->sc_poly.ensure(sizeof(ScPoly));
-  ScPoly *qh = (ScPoly *)c->sc_poly_host.ensure(sizeof(ScPoly));  // pinned: outlives the async copy
+  ScPoly *qd = (ScPoly *)c->sc.poly.ensure(sizeof(ScPoly));
+  ScPoly *qh = (ScPoly *)c->sc.poly_host.ensure(sizeof(ScPoly));  // pinned: outlives the async copy
   *qh = R.q;
   TNS_HIP(hipMemcpyAsync(qd, qh, sizeof(ScPoly), hipMemcpyHostToDevice, c->stream));
   R.q_dev = qd;
   // (sc_launch's grids: at most max_grid * 4 one-wave blocks)
-  R.partials = (Fr *)c->scratch[6].ensure(sizeof(Fr) * 4 * std::max<size_t>(max_blocks, (size_t)R.max_grid * 4));
-  R.counter = (unsigned *)c->sc_counter.ensure(sizeof(unsigned));
+  R.partials = (Fr *)c->sc.partials.ensure(sizeof(Fr) * 4 * std::max<size_t>(max_blocks, (size_t)R.max_grid * 4));
+  R.counter = (unsigned *)c->sc.counter.ensure(sizeof(unsigned));
   // zero once per sum-check (each round's last workgroup leaves it zero for the next round)
   TNS_HIP(hipMemsetAsync(R.counter, 0, sizeof(unsigned), c->stream));
-  c->sc_mapped.ensure(sizeof(ScResult));
-  ((volatile ScResult *)c->sc_mapped.p)->wait_expired = 0;  // (nothing of an earlier call is still running)
-  R.res_dev = (ScResult *)c->sc_mapped.dev;
-  R.chal = (ScChal *)c->sc_handoff.ensure(sizeof(ScChal));
-  R.chal_dev = (ScChal *)c->sc_handoff.dev;
-  R.rd = (ScRDev *)c->sc_rdev.ensure(sizeof(ScRDev));
+  c->sc.mapped.ensure(sizeof(ScResult));
+  ((volatile ScResult *)c->sc.mapped.p)->wait_expired = 0;  // (nothing of an earlier call is still running)
+  R.res_dev = (ScResult *)c->sc.mapped.dev;
+  R.chal = (ScChal *)c->sc.handoff.ensure(sizeof(ScChal));
+  R.chal_dev = (ScChal *)c->sc.handoff.dev;
+  R.rd = (ScRDev *)c->sc.rdev.ensure(sizeof(ScRDev));
   TNS_HIP(hipMemsetAsync(R.rd, 0, sizeof(ScRDev), c->stream));
   return R;
 }
@@ -970,7 +971,7 @@ static uint32_t sc_launch(ScRun &R, const ScTables &tt, size_t P) {
   // small rounds: one-wave workgroups spread over many CUs (a round of 2^8 pairs on one 256-thread
   // workgroup ran 35 us: one CU's multiply rate), large rounds: one round of resident 256-thread
   // workgroups, each thread looping over pairs
-  const uint32_t seq = ++R.c->sc_seq;
+  const uint32_t seq = ++R.c->sc.seq;
   hipStream_t st = R.c->stream;
   const size_t split_max = (size_t)1 << SC_SPLIT_LOG;
   if (P <= split_max) {  // four lanes a pair, 16 pairs a one-wave block (2^12-2^14 measured alike;
@@ -1115,8 +1116,8 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
   const size_t n = (size_t)1 << nv;
   Fr *bufB[MAX_SC_TABLES], *bufC[MAX_SC_TABLES];
   for (int i = 0; i < k; i++) {
-    bufB[i] = (Fr *)c->scratch[2 + i].ensure(sizeof(Fr) * (n / 2 + 1));
-    bufC[i] = (Fr *)c->sc_pong[i].ensure(sizeof(Fr) * (n / 4 + 1));
+    bufB[i] = (Fr *)c->scratch.sc_fold(i).ensure(sizeof(Fr) * (n / 2 + 1));
+    bufC[i] = (Fr *)c->sc.pong[i].ensure(sizeof(Fr) * (n / 4 + 1));
   }
   ScRun R = sc_run(c, k, terms, n_terms, grid_for(n / 2 + 1, 256, 2048));
   // round rr reads the caller's tables (rr <= 1) or the previous round's output and writes the
@@ -1125,8 +1126,8 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
     return rr <= 1 ? tables[R.perm[m]] : (rr % 2 == 0 ? bufB[R.perm[m]] : bufC[R.perm[m]]);
   };
   auto out_of = [&](unsigned rr, int m) -> Fr * { return rr % 2 == 1 ? bufB[R.perm[m]] : bufC[R.perm[m]]; };
-  const uint32_t chal_base = c->sc_chal_seq;
-  c->sc_chal_seq += nv + 1;
+  const uint32_t chal_base = c->sc.chal_seq;
+  c->sc.chal_seq += nv + 1;
   R.chal->flag = 0;  // (no stale value can match: chal_base + i is fresh)
   // the persistent tail (k_sc_tail) from the first round r0 >= 2 of <= 2^SC_PTAIL_LOG pairs
   unsigned r0 = nv;
@@ -1145,23 +1146,23 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
     }
   Fr *htab_dev = nullptr;
   if (rh < nv) {
-    c->sc_htab.ensure(sizeof(Fr) * k * (n >> rh));
-    htab_dev = (Fr *)c->sc_htab.dev;
+    c->sc.htab.ensure(sizeof(Fr) * k * (n >> rh));
+    htab_dev = (Fr *)c->sc.htab.dev;
   }
   uint32_t tail_seq = 0;
   // queue round rr (rr >= 1: behind the wait for challenge r_{rr-1}); rr == nv: the final fold
   auto queue = [&](unsigned rr) -> uint32_t {
     if (tail && rr >= r0) {  // rounds r0 .. nv - 1 and the final fold: one launch at r0
       if (rr == r0) {
-        ScTailSync *sync = (ScTailSync *)c->sc_tail_sync.ensure(sizeof(ScTailSync));
+        ScTailSync *sync = (ScTailSync *)c->sc.tail_sync.ensure(sizeof(ScTailSync));
         TNS_HIP(hipMemsetAsync(sync, 0, sizeof(ScTailSync), c->stream));
         ScPing pp{};
         for (int m = 0; m < k; m++) {
           pp.B[m] = bufB[R.perm[m]];
           pp.C[m] = bufC[R.perm[m]];
         }
-        tail_seq = c->sc_seq + 1;
-        c->sc_seq += nv - r0 + 1;
+        tail_seq = c->sc.seq + 1;
+        c->sc.seq += nv - r0 + 1;
         const unsigned g = (unsigned)std::min<size_t>(SC_PTAIL_BLOCKS, std::max<size_t>(1, (n >> (r0 + 1)) / 16));
 #define TNS_SC_K(K)                                                                                             \
   k_sc_tail<K><<<g, 64, 0, c->stream>>>(pp, R.q_dev, r0, nv, n, R.chal_dev, chal_base, R.res_dev, tail_seq, \
@@ -1185,7 +1186,7 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
     if (rr == nv) {
       // nv <= 1: the caller's tables (nv == 0 reads them as they are; nv - 1 would wrap)
       for (int m = 0; m < k; m++) tt.in[m] = nv <= 1 ? tables[R.perm[m]] : out_of(nv - 1, m);
-      const uint32_t seq = ++c->sc_seq;
+      const uint32_t seq = ++c->sc.seq;
       k_sc_final<<<1, 64, 0, c->stream>>>(tt, k, R.rd, nv > 0, R.res_dev, seq);
       TNS_LAUNCH_CHECK();
       return seq;
@@ -1226,7 +1227,7 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
       } else {
         if (rnd == rh) {
           sc_wait(c, seq);
-          H.load((const Fr *)c->sc_htab.p, k, n >> rh, R.perm, terms, n_terms);
+          H.load((const Fr *)c->sc.htab.p, k, n >> rh, R.perm, terms, n_terms);
         }
         H.sums(e);
       }
@@ -1261,7 +1262,7 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
         tr.prehash(tr.state.size() + (size_t)n1 + 4 * 32 + (size_t)n2);
       }
     }
-    const ScResult &res = rh < nv ? *(const ScResult *)c->sc_mapped.p : sc_wait(c, seq);
+    const ScResult &res = rh < nv ? *(const ScResult *)c->sc.mapped.p : sc_wait(c, seq);
 #if TNS_SC_TRACE
     t_seen[nv] = us();
     for (unsigned rnd = 0; rnd < nv; rnd++)
@@ -1316,8 +1317,8 @@ int sumcheck_prove_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const Fr &
   // tables are left intact (Twist / Shout open the same evaluation vectors afterwards).
   Fr *bufB[MAX_SC_TABLES], *bufC[MAX_SC_TABLES];
   for (int i = 0; i < k; i++) {
-    bufB[i] = (Fr *)c->scratch[2 + i].ensure(sizeof(Fr) * (n / 2 + 1));
-    bufC[i] = (Fr *)c->sc_pong[i].ensure(sizeof(Fr) * (n / 4 + 1));
+    bufB[i] = (Fr *)c->scratch.sc_fold(i).ensure(sizeof(Fr) * (n / 2 + 1));
+    bufC[i] = (Fr *)c->sc.pong[i].ensure(sizeof(Fr) * (n / 4 + 1));
   }
   ScRun R = sc_run(c, k, terms, n_terms, grid_for(n / 2 + 1, 256, 2048));
   // kernel order m = caller's table perm[m] (the composition's cheapest nesting)
@@ -1393,7 +1394,7 @@ int sumcheck_prove_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const Fr &
     // tail_rnd - 1 .. nv - 1 (the last one binds the final variable)
     const int m = (int)(nv - tail_rnd + 1);
     tail_ch[m - 1] = r_prev;
-    Fr *d_ch = R.partials, *d_out = (Fr *)c->scratch[7].ensure(sizeof(Fr) * MAX_SC_TABLES);
+    Fr *d_ch = R.partials, *d_out = (Fr *)c->sc.fold_out.ensure(sizeof(Fr) * MAX_SC_TABLES);
     TNS_HIP(hipMemcpyAsync(d_ch, tail_ch, sizeof(Fr) * m, hipMemcpyHostToDevice, c->stream));
     ScTail tl{};
     for (int i = 0; i < k; i++) {  // src may still be the caller's table (tail from round 1); perm is identity here
@@ -1411,11 +1412,11 @@ int sumcheck_prove_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const Fr &
   } else if (k > 0) {
     ScTables tt{};
     for (int m2 = 0; m2 < k; m2++) tt.in[m2] = src[m2];
-    const uint32_t seq = ++c->sc_seq;
+    const uint32_t seq = ++c->sc.seq;
     if (nv > 0) {  // (the challenge to device memory: k_sc_final reads it there)
       R.chal->r = r_prev;
-      __atomic_store_n(&R.chal->flag, ++c->sc_chal_seq, __ATOMIC_RELEASE);
-      k_sc_wait_r<<<1, 64, 0, c->stream>>>(R.chal_dev, c->sc_chal_seq, R.rd, R.res_dev);
+      __atomic_store_n(&R.chal->flag, ++c->sc.chal_seq, __ATOMIC_RELEASE);
+      k_sc_wait_r<<<1, 64, 0, c->stream>>>(R.chal_dev, c->sc.chal_seq, R.rd, R.res_dev);
       TNS_LAUNCH_CHECK();
     }
     k_sc_final<<<1, 64, 0, c->stream>>>(tt, k, R.rd, nv > 0, R.res_dev, seq);

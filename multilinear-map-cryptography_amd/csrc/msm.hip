@@ -36,7 +36,8 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
+#include "ctx.hpp"
+#include "srs.hpp"
 
 namespace tns {
 
@@ -600,39 +601,34 @@ static int table_window(size_t n) {
   return best_window(n, 254, 22, true, 0, 1.0);
 }
 
-FixedBase *fixed_base_build_dev(Ctx *c, const G1Affine *points, size_t n) {
-  FixedBase *fb = new FixedBase();
-  try {
-    fb->n = n;
-    fb->c = table_window(n);
-    fb->W = windows_for(254, fb->c);
-    G1Affine *T = (G1Affine *)fb->table.ensure(sizeof(G1Affine) * n * fb->W);
-    TNS_HIP(hipMemcpyAsync(T, points, sizeof(G1Affine) * n, hipMemcpyDeviceToDevice, c->stream));
-    const size_t slab = std::min(n, (size_t)1 << 22);
-    DevBuf xb, pb;
-    G1Xyzz *X = (G1Xyzz *)xb.ensure(sizeof(G1Xyzz) * slab);
-    Fq *pre = (Fq *)pb.ensure(sizeof(Fq) * slab);
-    for (size_t off = 0; off < n; off += slab) {
-      const size_t m = std::min(slab, n - off);
-      k_affine_to_xyzz<<<grid_for(m, 256), 256, 0, c->stream>>>(points + off, m, X);
+std::unique_ptr<FixedBase> fixed_base_build_dev(Ctx *c, const G1Affine *points, size_t n) {
+  auto fb = std::make_unique<FixedBase>();
+  fb->n = n;
+  fb->c = table_window(n);
+  fb->W = windows_for(254, fb->c);
+  G1Affine *T = (G1Affine *)fb->table.ensure(sizeof(G1Affine) * n * fb->W);
+  TNS_HIP(hipMemcpyAsync(T, points, sizeof(G1Affine) * n, hipMemcpyDeviceToDevice, c->stream));
+  const size_t slab = std::min(n, (size_t)1 << 22);
+  DevBuf xb, pb;
+  G1Xyzz *X = (G1Xyzz *)xb.ensure(sizeof(G1Xyzz) * slab);
+  Fq *pre = (Fq *)pb.ensure(sizeof(Fq) * slab);
+  for (size_t off = 0; off < n; off += slab) {
+    const size_t m = std::min(slab, n - off);
+    k_affine_to_xyzz<<<grid_for(m, 256), 256, 0, c->stream>>>(points + off, m, X);
+    TNS_LAUNCH_CHECK();
+    for (int j = 1; j < fb->W; j++) {
+      k_dbl_times<<<grid_for(m, 256), 256, 0, c->stream>>>(X, m, fb->c);
       TNS_LAUNCH_CHECK();
-      for (int j = 1; j < fb->W; j++) {
-        k_dbl_times<<<grid_for(m, 256), 256, 0, c->stream>>>(X, m, fb->c);
-        TNS_LAUNCH_CHECK();
-        xyzz_to_affine_batch_dev(c, X, m, T + (size_t)j * n + off, pre);
-      }
+      xyzz_to_affine_batch_dev(c, X, m, T + (size_t)j * n + off, pre);
     }
-    TNS_HIP(hipStreamSynchronize(c->stream));
-  } catch (...) {
-    delete fb;
-    throw;
   }
+  TNS_HIP(hipStreamSynchronize(c->stream));
   return fb;
 }
 
 // the window table if the device has room for it: on an allocation failure the MSMs over these
 // points run without one (per-window buckets, same results) and nothing is cached
-FixedBase *fixed_base_try_build(Ctx *c, const G1Affine *points, size_t n) {
+std::unique_ptr<FixedBase> fixed_base_try_build(Ctx *c, const G1Affine *points, size_t n) {
   try {
     return fixed_base_build_dev(c, points, n);
   } catch (const Error &e) {
@@ -646,7 +642,7 @@ const FixedBase *srs_fixed_base(Ctx *c, const Srs &srs, size_t n) {
   if (n < ((size_t)1 << 16) || !c->msm_tables) return nullptr;
   if (srs.held < n) return nullptr;  // a shard's table covers its held points (tns_msm_sharded)
   if (!srs.fb) srs.fb = fixed_base_try_build(c, srs.points.as<G1Affine>(), srs.held);
-  return srs.fb;
+  return srs.fb.get();
 }
 
 // ---------------------------------------------------------------- driver
@@ -685,6 +681,8 @@ struct MsmJob {
   int ks = 0, acc_k = 0;
   size_t nchunks = 0, n = 0;
   G1Xyzz *buckets = nullptr;  // set before the accumulation (a two-set tail: the pair's buckets adjoin)
+  const HeadTail *ht = nullptr;  // the accumulation's per-chunk partials and bucket bounds (the fixup reads them)
+  const uint2 *cbk = nullptr;
   // where msm_complete finds the per-set sums: the slot of res_lane (this lane, or the lane that ran
   // a two-set tail), set res_set of res_sets
   MsmLane *res_lane = nullptr;
@@ -771,7 +769,7 @@ const void *lane_wait(MsmLane &ln, int slot) {
 // the sort keeps its histograms when the bit length confirms the plan (else it recounts): one read
 // of the scalars and one launch less (C4's value commitment: k_scalar_bits 0.26 ms + the count).
 static SortInput bits_launch(MsmLane &ln, const Fr *scalars, size_t n) {
-  unsigned *d_bits = (unsigned *)ln.ws[4].ensure(2 * sizeof(unsigned));  // (then the sort's two counters)
+  unsigned *d_bits = (unsigned *)ln.msm.words.ensure(2 * sizeof(unsigned));
   TNS_HIP(hipMemsetAsync(d_bits, 0, sizeof(unsigned), ln.stream));
   SortInput in;
   in.fr = scalars;
@@ -842,7 +840,7 @@ static void msm_launch_sort(Ctx *ctx, MsmLane &ln, const G1Affine *points, const
     return;
   }
   if (n <= 64) {
-    G1Xyzz *d = (G1Xyzz *)ln.ws[0].ensure(sizeof(G1Xyzz));
+    G1Xyzz *d = (G1Xyzz *)ln.msm.tiny_out.ensure(sizeof(G1Xyzz));
     k_msm_tiny<<<1, 64, 0, st>>>(points, scalars, (int)n, d);
     TNS_LAUNCH_CHECK();
     const void *src[1] = {d};
@@ -887,7 +885,7 @@ static void msm_launch_sort(Ctx *ctx, MsmLane &ln, const G1Affine *points, const
   J.nchunks = (total + acc_k - 1) / acc_k;
   J.n = n;
   J.sort_prof.reset(new ProfScope(ctx->prof, st, "msm_sort", 32.0 * n + 16.0 * total));
-  J.valid = (uint32_t *)ln.ws[4].ensure(2 * sizeof(uint32_t));  // entries; [1]: a run crosses a chunk
+  J.valid = (uint32_t *)ln.msm.words.ensure(2 * sizeof(uint32_t));  // entries; [1]: a run crosses a chunk
   bucket_sort_begin(ln, in2, n, P.c, P.W, P.shared, (uint32_t)P.stride, P.end_bit - 1, J.valid, J.bs);
   J.sort_pending = true;
   J.passes_pending = true;
@@ -931,11 +929,13 @@ static void msm_launch_accumulate(Ctx *ctx, MsmJob &J, hipEvent_t accumulated, h
   }
   MsmLane &ln = *J.lane;
   hipStream_t st = on ? on : ln.stream;
-  if (!J.buckets) J.buckets = (G1Xyzz *)ln.ws[5].ensure(sizeof(G1Xyzz) * J.P.nb);
-  HeadTail *ht = (HeadTail *)ln.ws[6].ensure(sizeof(HeadTail) * J.nchunks);
+  if (!J.buckets) J.buckets = (G1Xyzz *)ln.msm.buckets.ensure(sizeof(G1Xyzz) * J.P.nb);
+  HeadTail *ht = (HeadTail *)ln.msm.head_tail.ensure(sizeof(HeadTail) * J.nchunks);
+  J.ht = ht;
   {
     TNS_PROF_ON(ctx, st, "msm_accumulate", 96.0 * J.n);  // 96 B per (scalar, point) pair
-    uint2 *cbk = (uint2 *)ln.ws[16].ensure(sizeof(uint2) * J.nchunks);
+    uint2 *cbk = (uint2 *)ln.msm.chunk_bounds.ensure(sizeof(uint2) * J.nchunks);
+    J.cbk = cbk;
     auto acc = J.keys2 ? k_accumulate<true> : k_accumulate<false>;
     acc<<<grid_for(J.nchunks, 256, 1u << 30), 256, 0, st>>>(J.keys2, J.vals2, J.valid, J.points, J.buckets, ht,
                                                             J.nchunks, J.ks, J.acc_k, J.bstart, J.P.nb, cbk,
@@ -982,12 +982,12 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
         F.n++;
       }
       if (F.n) {
-        G1Xyzz *base = (G1Xyzz *)X.lane->fix.ensure(sizeof(G1Xyzz) * off);
+        G1Xyzz *base = (G1Xyzz *)X.lane->msm.fix.ensure(sizeof(G1Xyzz) * off);
         size_t o = 0;
         for (int l = 1; l <= F.n; o += F.len[l], l++) F.lv[l] = base + o;
       }
       max_levels = std::max(max_levels, F.n);
-      FA.s[j] = FixupSet{X.bstart, X.bend, X.valid, (const HeadTail *)X.lane->ws[6].p, F, X.buckets, X.P.nb, X.acc_k};
+      FA.s[j] = FixupSet{X.bstart, X.bend, X.valid, X.ht, F, X.buckets, X.P.nb, X.acc_k};
       max_nb = std::max(max_nb, X.P.nb);
     }
     for (int l = 1; l <= max_levels; l++) {
@@ -996,7 +996,7 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
       for (int j = 0; j < nj; j++) {
         const FixLevels &F = FA.s[j].F;
         const MsmJob &X = *J[j];
-        LA.s[j] = FixLevelSet{X.valid, FA.s[j].ht, F.lv[l - 1], F.lv[l], (const uint2 *)X.lane->ws[16].p,
+        LA.s[j] = FixLevelSet{X.valid, FA.s[j].ht, F.lv[l - 1], F.lv[l], X.cbk,
                               l <= F.n ? F.len[l] : 0, X.acc_k};
         if (l <= F.n) max_groups = std::max(max_groups, F.len[l]);
       }
@@ -1025,7 +1025,7 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
   const int specs = nbits + 2;
   {
     TNS_PROF_ON(ctx, st, "msm_reduce", 128.0 * P.nb * nj);
-    G1Xyzz *T = (G1Xyzz *)run.ws[7].ensure(sizeof(G1Xyzz) * 2 * sets * (g1 + (L1 ? g : 0)));
+    G1Xyzz *T = (G1Xyzz *)run.msm.level_sums.ensure(sizeof(G1Xyzz) * 2 * sets * (g1 + (L1 ? g : 0)));
     G1Xyzz *S = T + (size_t)sets * g1;
     k_reduce_level<<<grid_for((size_t)sets * g1, 64, 1u << 30), 64, 0, st>>>(J[0]->buckets, sets, P.half, L0, T, S);
     TNS_LAUNCH_CHECK();
@@ -1042,7 +1042,7 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     const int CH = (int)std::min<size_t>(small_sets || L1 ? 8 : 16, g / 2);
     const size_t nch = g / (2 * (size_t)CH);
     const size_t nparts = (size_t)sets * specs * nch;
-    G1Xyzz *parts = (G1Xyzz *)run.ws[8].ensure(sizeof(G1Xyzz) * (2 * nparts + (size_t)sets * specs));
+    G1Xyzz *parts = (G1Xyzz *)run.msm.parts.ensure(sizeof(G1Xyzz) * (2 * nparts + (size_t)sets * specs));
     G1Xyzz *tmp = parts + nparts, *out = tmp + nparts;
     const bool tree = nch % 64 == 0;  // each wave adds its 64 chunk sums by a butterfly
     k_masked_sums<<<grid_for(nparts, 64, 1u << 30), 64, 0, st>>>(T, S, sets, g, nbits, CH, parts, tree);
@@ -1212,7 +1212,7 @@ static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz 
   msm_finish_sort(ja);
   Event acc_a, acc_b;
   // a two-set tail needs the pair's buckets adjoining: room for both before acc a writes the first
-  if (ja.sorted && ja.P.shared) ja.buckets = (G1Xyzz *)l0.ws[5].ensure(sizeof(G1Xyzz) * 2 * ja.P.nb);
+  if (ja.sorted && ja.P.shared) ja.buckets = (G1Xyzz *)l0.msm.buckets.ensure(sizeof(G1Xyzz) * 2 * ja.P.nb);
   TNS_HIP(hipStreamWaitEvent(as, sa, 0));
   msm_launch_accumulate(ctx, ja, acc_a, as);
   msm_finish_sort(jb);

@@ -127,14 +127,14 @@ __global__ void __launch_bounds__(256) k_pass_twiddles(const Fr *__restrict__ TW
 static const Fr *pass_table(Ctx *c, unsigned lo, unsigned r) {
   const uint32_t key = (lo << 8) | r;
   auto it = c->pass_tw.find(key);
-  if (it != c->pass_tw.end()) return it->second->as<Fr>();
+  if (it != c->pass_tw.end()) return it->second.as<Fr>();
   const Fr *TW = ntt_twiddles(c, lo + r);
   const size_t M = (size_t)1 << (lo + r);
-  DevBuf *b = new DevBuf();
-  Fr *t = (Fr *)b->ensure(sizeof(Fr) * 2 * M);
+  DevBuf b;
+  Fr *t = (Fr *)b.ensure(sizeof(Fr) * 2 * M);
   k_pass_twiddles<<<grid_for(M, 256), 256, 0, c->stream>>>(TW, lo, r, t, t + M);
   TNS_LAUNCH_CHECK();
-  c->pass_tw[key] = b;
+  c->pass_tw.emplace(key, std::move(b));
   return t;
 }
 

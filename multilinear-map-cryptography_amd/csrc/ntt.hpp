@@ -9,7 +9,7 @@
 // k-consecutive lanes of a pass read consecutive 32-byte entries (L2-resident; the
 // table for 2^25 is 1 GiB of HBM but each pass touches only its stages' slices).
 #pragma once
-#include "common.hpp"
+#include "ctx.hpp"
 
 namespace tns {
 

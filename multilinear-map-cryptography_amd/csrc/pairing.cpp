@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "common.hpp"
+#include "host.hpp"
 #include "hostfield.hpp"
 
 namespace tns {

@@ -14,7 +14,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.hpp"
+#include "ctx.hpp"
 
 namespace tns {
 
@@ -56,7 +56,7 @@ __global__ void k_scan_serial(const Fr *__restrict__ c, size_t n, Fr z, Fr *__re
   }
 }
 
-// out[t] = sum_{u >= t} c_u z^(u - t); uses scratch slots [base, base + depth)
+// out[t] = sum_{u >= t} c_u z^(u - t); level `depth` of the carries lives in the scratch of that name
 static void suffix_scan(Ctx *ctx, const Fr *c, size_t n, const Fr &z, Fr *out, int depth) {
   if (n == 0) return;
   if (n <= (size_t)SCAN_K) {
@@ -64,10 +64,10 @@ static void suffix_scan(Ctx *ctx, const Fr *c, size_t n, const Fr &z, Fr *out, i
     TNS_LAUNCH_CHECK();
     return;
   }
-  if (depth >= 6) throw Error(TNS_ERR_POLYNOMIAL, "suffix scan too deep");
+  if (depth >= SharedScratch::SCAN_LEVELS) throw Error(TNS_ERR_POLYNOMIAL, "suffix scan too deep");
   size_t C = (n + SCAN_K - 1) / SCAN_K;
   // two arrays of C per level in one allocation
-  Fr *L = (Fr *)ctx->scratch[depth].ensure(sizeof(Fr) * 2 * C);
+  Fr *L = (Fr *)ctx->scratch.scan_level(depth).ensure(sizeof(Fr) * 2 * C);
   Fr *S = L + C;
   TNS_PROF(ctx, "open_scan", 96.0 * n);
   k_scan_chunk_local<<<grid_for(C, 256, 1u << 30), 256, 0, ctx->stream>>>(c, n, z, L, C);
@@ -272,7 +272,7 @@ static const G1Affine *upload_fixed_base_table(Ctx *c) {
     std::lock_guard<std::mutex> lk(mu);
     if (host_table.empty()) host_table = build_fixed_base_table();
   }
-  G1Affine *d_table = (G1Affine *)c->scratch[0].ensure(sizeof(G1Affine) * host_table.size());
+  G1Affine *d_table = (G1Affine *)c->scratch.srs_table().ensure(sizeof(G1Affine) * host_table.size());
   TNS_HIP(hipMemcpyAsync(d_table, host_table.data(), sizeof(G1Affine) * host_table.size(),
                          hipMemcpyHostToDevice, c->stream));
   return d_table;
@@ -285,9 +285,9 @@ static void fixed_base_slabs(Ctx *c, size_t n, G1Affine *out, Fill fill) {
   if (!n) return;
   const G1Affine *d_table = upload_fixed_base_table(c);
   const size_t slab = (size_t)1 << 22;
-  Fr *pw = (Fr *)c->scratch[1].ensure(sizeof(Fr) * std::min(n, slab));
-  G1Xyzz *xy = (G1Xyzz *)c->scratch[2].ensure(sizeof(G1Xyzz) * std::min(n, slab));
-  Fq *pre = (Fq *)c->scratch[3].ensure(sizeof(Fq) * std::min(n, slab));
+  Fr *pw = (Fr *)c->scratch.srs_powers().ensure(sizeof(Fr) * std::min(n, slab));
+  G1Xyzz *xy = (G1Xyzz *)c->scratch.srs_xyzz().ensure(sizeof(G1Xyzz) * std::min(n, slab));
+  Fq *pre = (Fq *)c->scratch.srs_prefix().ensure(sizeof(Fq) * std::min(n, slab));
   for (size_t off = 0; off < n; off += slab) {
     size_t m = std::min(slab, n - off);
     const Fr *sc = fill(off, m, pw);

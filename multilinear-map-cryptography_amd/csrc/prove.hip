@@ -33,7 +33,7 @@ extern "C" {
 // flags (optional): the last of the mles as 0/1 bytes (sumcheck_zero_folds_async)
 static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *const *mles, int n_mles,
                              unsigned nv, EvalPoly &polyA, EvalPoly &polyB, tns_proof *out, double *timing,
-                             DevBuf &sbuf, Comm &m, const uint8_t *flags = nullptr, size_t n_flags = 0) {
+                             Comm &m, const uint8_t *flags = nullptr, size_t n_flags = 0) {
   Timer t_sc;
   unsigned lr = 0;
   while ((1 << lr) < m.size) lr++;
@@ -44,7 +44,7 @@ static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *con
   // alone yields the challenges: all nv rounds run on the host first ...
   const unsigned nv1 = nv ? nv : 1;
   std::vector<Fr> rounds(4 * (size_t)nv1, Fr::zero());
-  Fr *chal = (Fr *)c->sc_host.ensure(sizeof(Fr) * (nv1 + 4)), *vals = chal + nv1;
+  Fr *chal = (Fr *)c->sc.host.ensure(sizeof(Fr) * (nv1 + 4)), *vals = chal + nv1;
   char lab[64];
   for (unsigned rnd = 0; rnd < nv; rnd++) {
     snprintf(lab, sizeof lab, "sumcheck_round_%u", rnd);  // src/sumcheck.rs:90-96
@@ -60,7 +60,7 @@ static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *con
   // 49.32-49.51 ms per step, profiles/r04_ab_folds_at.txt)
   // (queued once the openings' barycentric pass is on the device: its launches come first, and the
   // folds' ~80 us of host launches run under its chain kernels, profiles/r06_hiptrace_gaps.txt)
-  Fr *d_vals = (Fr *)c->sc_out.ensure(sizeof(Fr) * 4);
+  Fr *d_vals = (Fr *)c->sc.out.ensure(sizeof(Fr) * 4);
   stream_wait(c->side, c->stream);  // the tables were written on the context stream
   bool folds_queued = false;
   auto queue_folds = [&]() {
@@ -96,8 +96,8 @@ static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *con
     std::memcpy(out->opening_point, &z, 32);
     Fr v[2];
     G1Affine pi[2];
-    open_evals_pair(c, srs, polyA, polyB, z, v, pi, sbuf, c->prove_ws[10], m, lr ? &fold_x : nullptr, folds_ready,
-                    queue_folds);
+    open_evals_pair(c, srs, polyA, polyB, z, v, pi, c->prove.open_s[0], c->prove.open_s[1], m, lr ? &fold_x : nullptr,
+                    folds_ready, queue_folds);
     folds_exchanged = lr > 0;
     store_proj(pi[0], out->opening_proofs[0]);
     store_proj(pi[1], out->opening_proofs[1]);
@@ -161,7 +161,7 @@ struct SideDrain {
 // protocol's labels), the sum-check and the openings, and the wait for the context stream.
 static void finish_proof(tns_ctx *ctx, const Srs &srs, const Timer &total, const G1Affine cm[2], const char *label0,
                          const char *label1, Fr *const *mles, int n_mles, unsigned nv, EvalPoly &polyA,
-                         EvalPoly &polyB, tns_proof *out, DevBuf &sbuf, Comm &m, const uint8_t *flags = nullptr,
+                         EvalPoly &polyB, tns_proof *out, Comm &m, const uint8_t *flags = nullptr,
                          size_t n_flags = 0) {
   store_proj(cm[0], out->commitments[0]);
   store_proj(cm[1], out->commitments[1]);
@@ -170,7 +170,7 @@ static void finish_proof(tns_ctx *ctx, const Srs &srs, const Timer &total, const
   tr.append_fr(commitment_hash(cm[0]));
   tr.append_label(label1);
   tr.append_fr(commitment_hash(cm[1]));
-  fill_common_tail(&ctx->c, srs, tr, mles, n_mles, nv, polyA, polyB, out, ctx->timing, sbuf, m, flags, n_flags);
+  fill_common_tail(&ctx->c, srs, tr, mles, n_mles, nv, polyA, polyB, out, ctx->timing, m, flags, n_flags);
   TNS_HIP(hipStreamSynchronize(ctx->c.stream));
   ctx->timing[5] = total.ms();
 }
@@ -202,14 +202,12 @@ static void twist_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   HostUpload upload(c);  // host inputs: addresses, flags, then values (under the address commitment)
   // ---- SoA extraction / padding into the resident workspace (src/twist.rs:115-148)
   Timer t_h2d;
-  DevBuf &d_addr_raw = c->prove_ws[0], &d_flags = c->prove_ws[1], &d_a = c->prove_ws[2],
-         &d_v = c->prove_ws[3], &d_o = c->prove_ws[4], &d_ca = c->prove_ws[5], &d_cv = c->prove_ws[6],
-         &d_s = c->prove_ws[7];
+  ProveWs &w = c->prove;
   // V: a resident full slice is used in place (nothing below writes it); host input or a
   // padded slice goes through the workspace
   const bool v_in_place = kind == hipMemcpyDeviceToDevice && n_ops == L;
-  Fr *A = (Fr *)d_a.ensure(sizeof(Fr) * L), *O = nullptr;
-  Fr *V = v_in_place ? (Fr *)const_cast<uint64_t *>(value) : (Fr *)d_v.ensure(sizeof(Fr) * L);
+  Fr *A = (Fr *)w.eval[0].ensure(sizeof(Fr) * L), *O = nullptr;
+  Fr *V = v_in_place ? (Fr *)const_cast<uint64_t *>(value) : (Fr *)w.eval[1].ensure(sizeof(Fr) * L);
   const uint64_t *ar = addr;
   const uint8_t *fl = is_write;
   // host inputs go through HostUpload (upload.cpp) on the copy stream, in the order the proof
@@ -230,11 +228,11 @@ static void twist_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   while ((1 << lr) < m.size) lr++;
   const bool flag_bytes = sumcheck_folds_take_flag_bytes(nv - lr);
   if (kind == hipMemcpyHostToDevice) {
-    uint64_t *dar = (uint64_t *)d_addr_raw.ensure(8 * (n_ops ? n_ops : 1));
-    uint8_t *dfl = (uint8_t *)d_flags.ensure(n_ops ? n_ops : 1);
+    uint64_t *dar = (uint64_t *)w.raw.ensure(8 * (n_ops ? n_ops : 1));
+    uint8_t *dfl = (uint8_t *)w.flags.ensure(n_ops ? n_ops : 1);
     if (n_ops) {
       // the addresses cross PCIe as u32 when they fit (memory sizes < 2^32: 64 MB fewer at 2^24 ops)
-      dar32 = (uint32_t *)c->prove_ws[11].ensure(4 * n_ops);
+      dar32 = (uint32_t *)w.narrow.ensure(4 * n_ops);
       up_a = upload.add_narrow(dar32, dar, addr, n_ops);
       // flags read by the folds only (after both commitments) go last: their copy then runs under
       // the last value chunk's MSM instead of ahead of the values
@@ -253,7 +251,7 @@ static void twist_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   }
   if (L > n_ops) fr_fill_zero_dev(c, V + n_ops, L - n_ops);
   if (!flag_bytes) {
-    O = (Fr *)d_o.ensure(sizeof(Fr) * L);
+    O = (Fr *)w.optype.ensure(sizeof(Fr) * L);
     if (up_f >= 0) upload.wait(up_f, st);
     stream_wait(c->side, st);
     k_write_flags<<<grid_for(L, 256), 256, 0, c->side>>>(fl, O, n_ops, L);
@@ -264,7 +262,7 @@ static void twist_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   // the address table (Montgomery, for the sum-check and the openings) and its bit length are
   // written on lane 0 as its MSM starts, so the value commitment's lane does not wait for them;
   // the commitment's sort reads the raw u64 addresses (8 bytes a scalar, no canonical copy)
-  unsigned *a_bits = (unsigned *)c->prove_ws[9].ensure(sizeof(unsigned));
+  unsigned *a_bits = (unsigned *)w.bits.ensure(sizeof(unsigned));
   ScalarSource src_a;
   src_a.prep = [=, &upload](hipStream_t s) {
     if (up_a >= 0) {
@@ -283,8 +281,8 @@ static void twist_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   pa.N = pv.N = N;
   pa.first = pv.first = first;
   pa.cnt = pv.cnt = L;
-  pa.coeffs = m.size == 1 ? (Fr *)d_ca.ensure(sizeof(Fr) * N) : nullptr;
-  pv.coeffs = m.size == 1 ? (Fr *)d_cv.ensure(sizeof(Fr) * N) : nullptr;
+  pa.coeffs = m.size == 1 ? (Fr *)w.coeff[0].ensure(sizeof(Fr) * N) : nullptr;
+  pv.coeffs = m.size == 1 ? (Fr *)w.coeff[1].ensure(sizeof(Fr) * N) : nullptr;
   pa.y = A;
   pv.y = V;
   tm[1] = t_int.ms();
@@ -308,7 +306,7 @@ static void twist_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   // ---- transcript (src/twist.rs:170-174), sum-check over the addr / value / op-type MLEs +
   // openings (src/twist.rs:177-243)
   Fr *mles[3] = {A, V, O};
-  finish_proof(ctx, srs->s, total, cm, "address_commitment", "value_commitment", mles, 3, nv, pa, pv, out, d_s, m,
+  finish_proof(ctx, srs->s, total, cm, "address_commitment", "value_commitment", mles, 3, nv, pa, pv, out, m,
                flag_bytes ? fl : nullptr, n_ops);
 }
 
@@ -366,9 +364,8 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   SideDrain drain{c};
   HostUpload upload(c);  // host inputs: lookup indices, then the table (under the index commitment)
   Timer t_h2d;
-  DevBuf &d_idx_raw = c->prove_ws[0], &d_bad = c->prove_ws[1], &d_t = c->prove_ws[2], &d_i = c->prove_ws[3],
-         &d_ct = c->prove_ws[5], &d_ci = c->prove_ws[6], &d_s = c->prove_ws[7];
-  Fr *TB = (Fr *)d_t.ensure(sizeof(Fr) * LT), *I = (Fr *)d_i.ensure(sizeof(Fr) * LM);
+  ProveWs &w = c->prove;
+  Fr *TB = (Fr *)w.eval[0].ensure(sizeof(Fr) * LT), *I = (Fr *)w.eval[1].ensure(sizeof(Fr) * LM);
   if (LT > n_entries) fr_fill_zero_dev(c, TB + n_entries, LT - n_entries);  // the padding (src/shout.rs:105-107)
   const bool t_late = kind == hipMemcpyHostToDevice && n_entries > 0;
   int up_i = -1, up_t = -1;
@@ -376,8 +373,8 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   uint32_t *dir32 = nullptr;
   if (kind == hipMemcpyHostToDevice) {
     if (n_lookups) {
-      uint64_t *dir = (uint64_t *)d_idx_raw.ensure(8 * n_lookups);
-      dir32 = (uint32_t *)c->prove_ws[11].ensure(4 * n_lookups);  // u32 over PCIe when they fit
+      uint64_t *dir = (uint64_t *)w.raw.ensure(8 * n_lookups);
+      dir32 = (uint32_t *)w.narrow.ensure(4 * n_lookups);  // u32 over PCIe when they fit
       up_i = upload.add_narrow(dir32, dir, indices, n_lookups);
       ir = dir;
     }
@@ -393,7 +390,7 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
       upload.wait(up_i, st);
       widen_dev(st, dir32, upload.narrow_width(up_i), n_lookups, const_cast<uint64_t *>(ir));
     }
-    unsigned *bad = (unsigned *)d_bad.ensure(sizeof(unsigned));
+    unsigned *bad = (unsigned *)w.flags.ensure(sizeof(unsigned));
     TNS_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned), st));
     k_max_index_check<<<grid_for(n_lookups, 256), 256, 0, st>>>(ir, n_lookups, n_entries_total, bad);
     TNS_LAUNCH_CHECK();
@@ -407,7 +404,7 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   if (kind == hipMemcpyHostToDevice) TNS_HIP(hipStreamSynchronize(st));
   tm[0] = t_h2d.ms();
   // the index table is written on lane 1 as the index commitment starts (see twist_core)
-  unsigned *i_bits = (unsigned *)c->prove_ws[9].ensure(sizeof(unsigned));
+  unsigned *i_bits = (unsigned *)w.bits.ensure(sizeof(unsigned));
   ScalarSource src_i;
   src_i.prep = [=](hipStream_t s) { u64_tables_dev(s, ir, n_lookups, LM, I, nullptr, i_bits); };
   src_i.canon_bits = i_bits;
@@ -421,8 +418,8 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   pi.first = firstM;
   pt.cnt = LT;
   pi.cnt = LM;
-  pt.coeffs = m.size == 1 ? (Fr *)d_ct.ensure(sizeof(Fr) * T) : nullptr;
-  pi.coeffs = m.size == 1 ? (Fr *)d_ci.ensure(sizeof(Fr) * M) : nullptr;
+  pt.coeffs = m.size == 1 ? (Fr *)w.coeff[0].ensure(sizeof(Fr) * T) : nullptr;
+  pi.coeffs = m.size == 1 ? (Fr *)w.coeff[1].ensure(sizeof(Fr) * M) : nullptr;
   pt.y = TB;
   pi.y = I;  // the sum-check leaves its input tables intact (mle.hip)
   tm[1] = t_int.ms();
@@ -449,7 +446,7 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   }
   tm[2] = t_com.ms();
   Fr *mles[1] = {I};  // the closure evaluates only the index MLE (src/shout.rs:175)
-  finish_proof(ctx, srs->s, total, cm, "table_commitment", "index_commitment", mles, 1, nv, pt, pi, out, d_s, m);
+  finish_proof(ctx, srs->s, total, cm, "table_commitment", "index_commitment", mles, 1, nv, pt, pi, out, m);
 }
 
 int tns_shout_prove(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *entries,

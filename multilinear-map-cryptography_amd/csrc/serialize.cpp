@@ -13,7 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "common.hpp"
+#include "hip_util.hpp"
+#include "host.hpp"
 
 namespace tns {
 

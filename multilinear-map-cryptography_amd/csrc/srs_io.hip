@@ -262,7 +262,7 @@ void lagrange_basis_attach_dev(Ctx *c, const Srs &srs, const uint8_t *bytes, siz
     throw Error(TNS_ERR_DEVICE, "no randomness from the OS for the Lagrange basis check");
   }
   hipStream_t st = c->stream;
-  LagrangeBasis *basis = new LagrangeBasis();
+  auto basis = std::make_unique<LagrangeBasis>();
   try {
     G1Affine *pts = (G1Affine *)basis->points.ensure(sizeof(G1Affine) * N);
     g1_decode_dev(c, bytes, N, compressed, pts);
@@ -277,16 +277,12 @@ void lagrange_basis_attach_dev(Ctx *c, const Srs &srs, const uint8_t *bytes, siz
     if (!(lhs.x == rhs.x) || !(lhs.y == rhs.y))
       throw Error(TNS_ERR_INVALID_PARAMETERS, "Lagrange basis does not match g1_powers");
     const auto key = std::make_tuple(N, (size_t)0, N);
-    if (srs.lagrange.count(key)) {
-      delete basis;
-      return;
-    }
+    if (srs.lagrange.count(key)) return;
     if (N >= ((size_t)1 << 12)) basis->fb = fixed_base_try_build(c, pts, N);
     TNS_HIP(hipStreamSynchronize(st));
-    srs.lagrange[key] = basis;
+    srs.lagrange[key] = std::move(basis);
   } catch (...) {
     (void)hipStreamSynchronize(st);  // nothing queued may outlive the buffers freed here
-    delete basis;
     throw;
   }
 }

@@ -31,8 +31,10 @@
 #include <thread>
 #include <vector>
 
-#include "common.hpp"
+#include "ctx.hpp"
+#include "group_ntt.hpp"
 #include "ntt.hpp"
+#include "srs.hpp"
 
 namespace tns {
 
@@ -40,7 +42,7 @@ namespace {
 
 constexpr size_t TF_DIRECT_H = 4;  // children of <= 4 nodes: direct correlation (h scalar mults / output)
 // (the launch bounds TF_WAVES / TF_NTT_WAVES, the lazy-domain scalar multiplication xyzz_mul_canon and
-// the split twiddle GlvScalar are in common.hpp: vc_open.hip runs the same group NTT)
+// the split twiddle GlvScalar are in group_ntt.hpp: vc_open.hip runs the same group NTT)
 
 // ---- GLV: phi(x, y) = (beta x, y) equals lambda (x, y) on G1 (beta a primitive cube root of unity
 // in Fq, lambda the matching one in Fr: phi(G) = lambda G, checked against the C oracle when the
@@ -48,7 +50,7 @@ constexpr size_t TF_DIRECT_H = 4;  // children of <= 4 nodes: direct correlation
 // |k1|, |k2| < 2^127: half the doublings of a 254-bit double-and-add.  The group NTT's twiddles are
 // split once per basis build on the host (Babai rounding in the reduced lattice basis
 // (a1, b1), (a2, b2) of {(a, b): a + b lambda = 0 mod r}; g1 = floor(b2 2^256 / r),
-// g2 = floor(-b1 2^256 / r)).  (GlvScalar: common.hpp)
+// g2 = floor(-b1 2^256 / r)).  (GlvScalar: group_ntt.hpp)
 // beta in Montgomery form (canonical 0x30644e72e131a0295e6dd9e7e0acccb0c28f069fbb966e3de4bd44e5607cfd48)
 __constant__ uint32_t kGlvBeta[8] = {0x13e80b9cu, 0x3350c88eu, 0xdb5e56b9u, 0x7dce557cu,
                                      0xb615564au, 0x6001b4b8u, 0x020217e0u, 0x2682e617u};
@@ -399,95 +401,89 @@ const LagrangeBasis *lagrange_basis_from_powers_dev(Ctx *c, const Srs &srs, size
     throw Error(TNS_ERR_INVALID_PARAMETERS, "the basis of N nodes needs g1_powers[0..N) (an unsharded SRS)");
   const auto key = std::make_tuple(N, (size_t)0, N);
   auto it = srs.lagrange.find(key);
-  if (it != srs.lagrange.end()) return it->second;
+  if (it != srs.lagrange.end()) return it->second.get();
   hipStream_t st = c->stream;
   const unsigned n = ilog2_exact(N);
   const G1Affine *g = srs.points.as<G1Affine>();
-  LagrangeBasis *basis = new LagrangeBasis();
-  try {
-    G1Affine *pts = (G1Affine *)basis->points.ensure(sizeof(G1Affine) * N);
-    if (N == 1) {  // L_0 = 1
-      TNS_HIP(hipMemcpyAsync(pts, g, sizeof(G1Affine), hipMemcpyDeviceToDevice, st));
-    } else {
-      const Fr *TW = ntt_twiddles(c, n);
-      // scalar side: every level of the subproduct tree (children of size h = 2^e, e < n)
-      DevBuf lcb, ab, bb;
-      Fr *Lc = (Fr *)lcb.ensure(sizeof(Fr) * N * n);
-      const unsigned gN = grid_for(N, 256, 1u << 20);
-      k_tf_leaves<<<gN, 256, 0, st>>>(N, Lc);
-      TNS_LAUNCH_CHECK();
-      Fr *A = (Fr *)ab.ensure(sizeof(Fr) * N), *B = (Fr *)bb.ensure(sizeof(Fr) * N);
-      for (unsigned e = 0; e + 1 < n; e++) {
-        const size_t h = (size_t)1 << e;
-        const Fr *Lin = Lc + (size_t)e * N;
-        Fr *Lout = Lc + (size_t)(e + 1) * N;
-        if (h <= 32) {
-          k_tf_poly_direct<<<gN, 256, 0, st>>>(Lin, N, h, Lout);
-          TNS_LAUNCH_CHECK();
-        } else {  // a b by a cyclic product of length 2h (deg a b <= 2h - 2: no wrap)
-          k_tf_pad2<<<gN, 256, 0, st>>>(Lin, N, h, A, B);
-          TNS_LAUNCH_CHECK();
-          fr_ntt(st, A, N, 2 * h, TW, false);
-          fr_ntt(st, B, N, 2 * h, TW, false);
-          k_tf_pmul<<<gN, 256, 0, st>>>(A, B, N, inv(from_u64<FrCfg>((uint64_t)(2 * h))));
-          TNS_LAUNCH_CHECK();
-          fr_ntt(st, A, N, 2 * h, TW, true);
-          k_tf_poly_finish<<<gN, 256, 0, st>>>(Lin, A, N, h, Lout);
-          TNS_LAUNCH_CHECK();
-        }
-      }
-      // group side, root to leaves: H holds every node's vector of the current level
-      DevBuf tgb;
-      glv_twiddles(c, TW, N, tgb);
-      const GlvScalar *TG = tgb.as<GlvScalar>();
-      DevBuf hb, hh, yb;
-      G1Xyzz *H = (G1Xyzz *)hb.ensure(sizeof(G1Xyzz) * N), *Hh = (G1Xyzz *)hh.ensure(sizeof(G1Xyzz) * N);
-      k_tf_from_affine<<<gN, 256, 0, st>>>(g, N, H);
-      TNS_LAUNCH_CHECK();
-      const unsigned gS = grid_for(N, 256, 4096);  // scalar-multiplication kernels: whole waves of work
-      G1Xyzz *Y = nullptr;
-      for (int e = (int)n - 1; e >= 0; e--) {
-        const size_t h = (size_t)1 << e, M = 2 * h;
-        const Fr *Le = Lc + (size_t)e * N;  // the children's ell
-        if (h <= TF_DIRECT_H) {
-          k_tf_level_direct<<<gS, 256, 0, st>>>(H, Le, N, h, Hh);
-          TNS_LAUNCH_CHECK();
-          std::swap(H, Hh);
-          continue;
-        }
-        if (!Y) Y = (G1Xyzz *)yb.ensure(sizeof(G1Xyzz) * N);
-        k_tf_rev_pad<<<gN, 256, 0, st>>>(Le, N, h, A, B);  // A = SL (left child's ell), B = SR
+  auto basis = std::make_unique<LagrangeBasis>();
+  G1Affine *pts = (G1Affine *)basis->points.ensure(sizeof(G1Affine) * N);
+  if (N == 1) {  // L_0 = 1
+    TNS_HIP(hipMemcpyAsync(pts, g, sizeof(G1Affine), hipMemcpyDeviceToDevice, st));
+  } else {
+    const Fr *TW = ntt_twiddles(c, n);
+    // scalar side: every level of the subproduct tree (children of size h = 2^e, e < n)
+    DevBuf lcb, ab, bb;
+    Fr *Lc = (Fr *)lcb.ensure(sizeof(Fr) * N * n);
+    const unsigned gN = grid_for(N, 256, 1u << 20);
+    k_tf_leaves<<<gN, 256, 0, st>>>(N, Lc);
+    TNS_LAUNCH_CHECK();
+    Fr *A = (Fr *)ab.ensure(sizeof(Fr) * N), *B = (Fr *)bb.ensure(sizeof(Fr) * N);
+    for (unsigned e = 0; e + 1 < n; e++) {
+      const size_t h = (size_t)1 << e;
+      const Fr *Lin = Lc + (size_t)e * N;
+      Fr *Lout = Lc + (size_t)(e + 1) * N;
+      if (h <= 32) {
+        k_tf_poly_direct<<<gN, 256, 0, st>>>(Lin, N, h, Lout);
         TNS_LAUNCH_CHECK();
-        fr_ntt(st, A, N, M, TW, false);
-        fr_ntt(st, B, N, M, TW, false);
-        const Fr iM = inv(from_u64<FrCfg>((uint64_t)M));
-        k_tf_scale_canon<<<gN, 256, 0, st>>>(A, N, iM);
-        k_tf_scale_canon<<<gN, 256, 0, st>>>(B, N, iM);
+      } else {  // a b by a cyclic product of length 2h (deg a b <= 2h - 2: no wrap)
+        k_tf_pad2<<<gN, 256, 0, st>>>(Lin, N, h, A, B);
         TNS_LAUNCH_CHECK();
-        TNS_HIP(hipMemcpyAsync(Hh, H, sizeof(G1Xyzz) * N, hipMemcpyDeviceToDevice, st));
-        g_ntt(st, Hh, N, M, TG, false);
-        k_tf_pointwise<<<gS, 256, 0, st>>>(Hh, A, B, N, Y);  // Y: left child (SR), Hh: right child (SL)
+        fr_ntt(st, A, N, 2 * h, TW, false);
+        fr_ntt(st, B, N, 2 * h, TW, false);
+        k_tf_pmul<<<gN, 256, 0, st>>>(A, B, N, inv(from_u64<FrCfg>((uint64_t)(2 * h))));
         TNS_LAUNCH_CHECK();
-        g_ntt(st, Y, N, M, TG, true);
-        g_ntt(st, Hh, N, M, TG, true);
-        k_tf_take<<<gN, 256, 0, st>>>(Y, Hh, N, h, H);
+        fr_ntt(st, A, N, 2 * h, TW, true);
+        k_tf_poly_finish<<<gN, 256, 0, st>>>(Lin, A, N, h, Lout);
         TNS_LAUNCH_CHECK();
       }
-      // H[j] = Q_j;  Lambda_j = w_j Q_j, then affine
-      k_tf_weights<<<gS, 256, 0, st>>>(H, bary_weights_dev(c, N, 0, N), N);
-      TNS_LAUNCH_CHECK();
-      DevBuf pre;
-      xyzz_to_affine_batch_dev(c, H, N, pts, (Fq *)pre.ensure(sizeof(Fq) * N));
-      TNS_HIP(hipStreamSynchronize(st));
     }
-    if (N >= ((size_t)1 << 12)) basis->fb = fixed_base_try_build(c, pts, N);
+    // group side, root to leaves: H holds every node's vector of the current level
+    DevBuf tgb;
+    glv_twiddles(c, TW, N, tgb);
+    const GlvScalar *TG = tgb.as<GlvScalar>();
+    DevBuf hb, hh, yb;
+    G1Xyzz *H = (G1Xyzz *)hb.ensure(sizeof(G1Xyzz) * N), *Hh = (G1Xyzz *)hh.ensure(sizeof(G1Xyzz) * N);
+    k_tf_from_affine<<<gN, 256, 0, st>>>(g, N, H);
+    TNS_LAUNCH_CHECK();
+    const unsigned gS = grid_for(N, 256, 4096);  // scalar-multiplication kernels: whole waves of work
+    G1Xyzz *Y = nullptr;
+    for (int e = (int)n - 1; e >= 0; e--) {
+      const size_t h = (size_t)1 << e, M = 2 * h;
+      const Fr *Le = Lc + (size_t)e * N;  // the children's ell
+      if (h <= TF_DIRECT_H) {
+        k_tf_level_direct<<<gS, 256, 0, st>>>(H, Le, N, h, Hh);
+        TNS_LAUNCH_CHECK();
+        std::swap(H, Hh);
+        continue;
+      }
+      if (!Y) Y = (G1Xyzz *)yb.ensure(sizeof(G1Xyzz) * N);
+      k_tf_rev_pad<<<gN, 256, 0, st>>>(Le, N, h, A, B);  // A = SL (left child's ell), B = SR
+      TNS_LAUNCH_CHECK();
+      fr_ntt(st, A, N, M, TW, false);
+      fr_ntt(st, B, N, M, TW, false);
+      const Fr iM = inv(from_u64<FrCfg>((uint64_t)M));
+      k_tf_scale_canon<<<gN, 256, 0, st>>>(A, N, iM);
+      k_tf_scale_canon<<<gN, 256, 0, st>>>(B, N, iM);
+      TNS_LAUNCH_CHECK();
+      TNS_HIP(hipMemcpyAsync(Hh, H, sizeof(G1Xyzz) * N, hipMemcpyDeviceToDevice, st));
+      g_ntt(st, Hh, N, M, TG, false);
+      k_tf_pointwise<<<gS, 256, 0, st>>>(Hh, A, B, N, Y);  // Y: left child (SR), Hh: right child (SL)
+      TNS_LAUNCH_CHECK();
+      g_ntt(st, Y, N, M, TG, true);
+      g_ntt(st, Hh, N, M, TG, true);
+      k_tf_take<<<gN, 256, 0, st>>>(Y, Hh, N, h, H);
+      TNS_LAUNCH_CHECK();
+    }
+    // H[j] = Q_j;  Lambda_j = w_j Q_j, then affine
+    k_tf_weights<<<gS, 256, 0, st>>>(H, bary_weights_dev(c, N, 0, N), N);
+    TNS_LAUNCH_CHECK();
+    DevBuf pre;
+    xyzz_to_affine_batch_dev(c, H, N, pts, (Fq *)pre.ensure(sizeof(Fq) * N));
     TNS_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    delete basis;
-    throw;
   }
-  srs.lagrange[key] = basis;
-  return basis;
+  if (N >= ((size_t)1 << 12)) basis->fb = fixed_base_try_build(c, pts, N);
+  TNS_HIP(hipStreamSynchronize(st));
+  return (srs.lagrange[key] = std::move(basis)).get();
 }
 
 }  // namespace tns

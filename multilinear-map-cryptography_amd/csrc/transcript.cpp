@@ -11,7 +11,7 @@
 // sum-check round); it is a few KB and costs microseconds.
 #include <cstring>
 
-#include "common.hpp"
+#include "host.hpp"
 
 namespace tns {
 

@@ -28,7 +28,7 @@
 #include <thread>
 #include <vector>
 
-#include "common.hpp"
+#include "ctx.hpp"
 
 namespace tns {
 

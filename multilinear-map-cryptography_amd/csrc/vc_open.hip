@@ -19,6 +19,7 @@
 // whose index order is the same.  Per call: n + M + 2 n variable-base scalar multiplications around
 // M log M butterfly ones -- O(n log n) for any n, no power of two required.
 #include "abi.hpp"
+#include "group_ntt.hpp"
 #include "ntt.hpp"
 
 namespace tns {
@@ -159,53 +160,47 @@ void check_vector(const Srs &srs, size_t n) {
 
 const OpenAllPlan *open_all_plan_dev(Ctx *c, const Srs &srs, size_t n) {
   auto it = srs.open_all.find(n);
-  if (it != srs.open_all.end()) return it->second;
+  if (it != srs.open_all.end()) return it->second.get();
   const LagrangeBasis *basis = basis_for(c, srs, n);
   if (n > ((size_t)1 << 26)) throw Error(TNS_ERR_INVALID_PARAMETERS, "all-index openings of more than 2^26 entries");
-  OpenAllPlan *P = new OpenAllPlan();
-  try {
-    P->n = n;
-    P->M = next_pow2(2 * n - 1);
-    if (n > 1) {  // (n == 1: the one proof is the identity)
-      const size_t M = P->M;
-      hipStream_t st = c->stream;
-      const GlvScalar *TG = nullptr;
-      const Fr *TW = transform_tables(c, ilog2_exact(M), &TG);
-      const Fr *w = bary_weights_dev(c, n, 0, n);
-      DevBuf fb, ifb, wb, xb, pre;
-      Fr *fact = (Fr *)fb.ensure(sizeof(Fr) * n), *ifact = (Fr *)ifb.ensure(sizeof(Fr) * n);
-      factorial_tables_dev(c, n, fact, ifact);
-      Fr *spec = (Fr *)P->spec.ensure(sizeof(Fr) * M);
-      const unsigned gM = grid_for(M, 256, 1u << 20), gn = grid_for(n, 256, 1u << 20);
-      k_vo_kernel<<<gM, 256, 0, st>>>(fact, ifact, n, M, spec);
-      TNS_LAUNCH_CHECK();
-      fr_ntt(st, spec, M, M, TW, false);
-      k_vo_scale<<<gM, 256, 0, st>>>(spec, M, inv(from_u64<FrCfg>((uint64_t)M)));
-      TNS_LAUNCH_CHECK();
-      // the scalars of f' that do not depend on the vector
-      Fr *Wc = (Fr *)wb.ensure(sizeof(Fr) * M);
-      k_vo_weighted<<<gM, 256, 0, st>>>(w, nullptr, n, M, Wc);
-      TNS_LAUNCH_CHECK();
-      fr_correlate(c, Wc, M, spec, TW);
-      k_vo_plan_scalars<<<gn, 256, 0, st>>>(fact, Wc, n, (Fr *)P->iw.ensure(sizeof(Fr) * n),
-                                            (Fr *)P->D.ensure(sizeof(Fr) * n));
-      TNS_LAUNCH_CHECK();
-      // A = Lambda * c
-      G1Xyzz *X = (G1Xyzz *)xb.ensure(sizeof(G1Xyzz) * M);
-      k_vo_points<<<gn, 256, 0, st>>>(basis->points.as<G1Affine>(), nullptr, n, X);
-      k_vo_pad<<<grid_for(M - n, 256, 1u << 20), 256, 0, st>>>(X, n, M);
-      TNS_LAUNCH_CHECK();
-      group_correlate(c, X, M, spec, TG);
-      xyzz_to_affine_batch_dev(c, X, n, (G1Affine *)P->A.ensure(sizeof(G1Affine) * n),
-                               (Fq *)pre.ensure(sizeof(Fq) * n));
-      TNS_HIP(hipStreamSynchronize(st));  // the scratch dies here
-    }
-  } catch (...) {
-    delete P;
-    throw;
+  auto P = std::make_unique<OpenAllPlan>();
+  P->n = n;
+  P->M = next_pow2(2 * n - 1);
+  if (n > 1) {  // (n == 1: the one proof is the identity)
+    const size_t M = P->M;
+    hipStream_t st = c->stream;
+    const GlvScalar *TG = nullptr;
+    const Fr *TW = transform_tables(c, ilog2_exact(M), &TG);
+    const Fr *w = bary_weights_dev(c, n, 0, n);
+    DevBuf fb, ifb, wb, xb, pre;
+    Fr *fact = (Fr *)fb.ensure(sizeof(Fr) * n), *ifact = (Fr *)ifb.ensure(sizeof(Fr) * n);
+    factorial_tables_dev(c, n, fact, ifact);
+    Fr *spec = (Fr *)P->spec.ensure(sizeof(Fr) * M);
+    const unsigned gM = grid_for(M, 256, 1u << 20), gn = grid_for(n, 256, 1u << 20);
+    k_vo_kernel<<<gM, 256, 0, st>>>(fact, ifact, n, M, spec);
+    TNS_LAUNCH_CHECK();
+    fr_ntt(st, spec, M, M, TW, false);
+    k_vo_scale<<<gM, 256, 0, st>>>(spec, M, inv(from_u64<FrCfg>((uint64_t)M)));
+    TNS_LAUNCH_CHECK();
+    // the scalars of f' that do not depend on the vector
+    Fr *Wc = (Fr *)wb.ensure(sizeof(Fr) * M);
+    k_vo_weighted<<<gM, 256, 0, st>>>(w, nullptr, n, M, Wc);
+    TNS_LAUNCH_CHECK();
+    fr_correlate(c, Wc, M, spec, TW);
+    k_vo_plan_scalars<<<gn, 256, 0, st>>>(fact, Wc, n, (Fr *)P->iw.ensure(sizeof(Fr) * n),
+                                          (Fr *)P->D.ensure(sizeof(Fr) * n));
+    TNS_LAUNCH_CHECK();
+    // A = Lambda * c
+    G1Xyzz *X = (G1Xyzz *)xb.ensure(sizeof(G1Xyzz) * M);
+    k_vo_points<<<gn, 256, 0, st>>>(basis->points.as<G1Affine>(), nullptr, n, X);
+    k_vo_pad<<<grid_for(M - n, 256, 1u << 20), 256, 0, st>>>(X, n, M);
+    TNS_LAUNCH_CHECK();
+    group_correlate(c, X, M, spec, TG);
+    xyzz_to_affine_batch_dev(c, X, n, (G1Affine *)P->A.ensure(sizeof(G1Affine) * n),
+                             (Fq *)pre.ensure(sizeof(Fq) * n));
+    TNS_HIP(hipStreamSynchronize(st));  // the scratch dies here
   }
-  srs.open_all[n] = P;
-  return P;
+  return (srs.open_all[n] = std::move(P)).get();
 }
 
 void vc_open_all_dev(Ctx *c, const Srs &srs, const Fr *vec, size_t n, G1Affine *proofs) {

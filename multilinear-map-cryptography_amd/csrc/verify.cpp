@@ -9,7 +9,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "host.hpp"
 #include "hostfield.hpp"
 
 namespace tns {

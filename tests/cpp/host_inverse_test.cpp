@@ -1,6 +1,6 @@
 // CPU test (tests/test_host_field.py): the host binary extended-Euclid inverse (bn254.hpp inv_binary_host)
 // against the Fermat chain a^(M-2) for Fr and Fq, 2000 random elements each plus 0 and 1.
-#include "common.hpp"
+#include "bn254.hpp"
 #include <random>
 #include <chrono>
 using namespace tns;
