@@ -342,6 +342,7 @@ TNS_HD Fp<C> pow_u64(const Fp<C> &a, u64 e) {
 // 130 single-bit products of square-and-multiply), squarings with the dedicated lazy square,
 // everything in the lazy [0, 2M) domain until the final conditional subtraction.  The chain
 // is read from constant memory with a uniform index: the walk is uniform control flow.
+// a in [0, 2M) (a lazy value is fine); the result is canonical, and 0 for a in {0, M}.
 template <class C>
 __device__ __forceinline__ Fp<C> inv_window_dev(const Fp<C> &a) {
   const Fp<C> a2 = sqr_lazy_dev(a);
@@ -365,6 +366,9 @@ __device__ __forceinline__ Fp<C> inv_window_dev(const Fp<C> &a) {
 // (the inputs are public), x^-1 = a^-1 R^-1, then one Montgomery product with R^3 gives
 // a^-1 R.  About 2 log2 M shift steps and log2 M subtractions of 8-limb words: ~4x fewer
 // instructions than the Fermat chain's ~310 products.  Inverse of zero is zero.
+// PRECONDITION: a in [0, M), canonical (k_chain_inv passes a canonical product).  On a = M, or
+// any multiple of M, the loop below reaches u = 0 and never ends: callers holding a lazy
+// [0, 2M) value reduce it first (the host twin inv_binary_host does so itself).
 template <class C>
 __device__ __forceinline__ void limbs_half_mod(u32 (&x)[8]) {  // x / 2 mod M (x < M)
   if (x[0] & 1u) {  // x + M < 2^255: no carry out of the top limb
@@ -683,7 +687,10 @@ TNS_HD G1Xyzz xyzz_madd(const G1Xyzz &p, const G1Affine &q) {
 // the running sum live in [0, 2M): products skip their final conditional subtraction
 // (inputs < 2M give results < 2M since 4M < 2^256), sums and differences reduce against 2M,
 // and "is zero mod M" is {0, M}.  The affine input is canonical; xyzz_canon brings a sum
-// back to [0, M) before anything else reads it.
+// back to [0, M) before anything else reads it.  Every identity these formulas RETURN is
+// G1Xyzz::inf() or a copy of an operand, and a finite result's zz is a product of values nonzero
+// mod M, so zz = M arises only where a caller supplies it: xyzz_add_lazy, xyzz_dbl_lazy and
+// xyzz_mul_canon accept both forms, xyzz_madd_lazy's accumulator p only zz == 0 (p.is_inf()).
 __device__ __forceinline__ bool fq_zero_lazy(const Fq &a) {
   u32 z = 0, m = 0;
 #pragma unroll
@@ -695,7 +702,11 @@ __device__ __forceinline__ bool fq_zero_lazy(const Fq &a) {
 }
 
 // K - a for a constant K >= a (no borrow out, no correction): K = M negates a canonical value,
-// K = 2M forms the lazy-domain negation of a value in [0, 2M).  a is tied to the result (no
+// K = 2M forms the lazy-domain negation of a value in [0, 2M): the result lies in (0, 2M], and it
+// is 2M itself -- outside [0, 2M) -- exactly for a = 0.  The point formulas below pass values that
+// are nonzero mod M (PPP, W of a finite, non-doubling step), so theirs stay below 2M; mle.hip's
+// round kernel works in the closed [0, 2M], which every lazy function here maps into itself.
+// a in [0, K] in either case.  a is tied to the result (no
 // early-clobber operand, see field_asm.inc); the borrow-chain limbs of K come from VGPRs (one
 // constant-bus read per VALU instruction on gfx9: VCC is already one).
 template <class C, bool TWO_M>

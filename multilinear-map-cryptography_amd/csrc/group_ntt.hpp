@@ -53,7 +53,8 @@ __device__ __forceinline__ G1Xyzz xyzz_dbl_lazy(const G1Xyzz &p) {
   return r;
 }
 
-// k P for a canonical scalar k: left to right from k's top bit.  Where the lanes of a wave share
+// k P for a canonical scalar k (the plain integer, not its Montgomery form, below r) and P with
+// coordinates in [0, 2M); the result is canonical.  Left to right from k's top bit.  Where the lanes of a wave share
 // k (the group NTT maps equal twiddles to one wave), the branches are uniform.
 static __device__ G1Xyzz xyzz_mul_canon(const G1Xyzz &P, const Fr &k) {
   G1Xyzz acc = G1Xyzz::inf();

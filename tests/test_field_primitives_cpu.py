@@ -1,0 +1,186 @@
+"""The big-integer reference and operand sets of the device field tests (tests/fieldref.py), checked
+without a GPU: (a) the Montgomery constants of bn254.hpp equal the ones derived from the moduli;
+(b) the exact lazy results (a b + m M) / R and (a b + c d + m M) / R stay inside the ranges the
+device functions promise, over the full operand sets, so the range assertions of
+test_gpu_field_primitives.py are satisfiable; (c) the library's host twins, compiled host-only
+from its own headers, agree with the reference on the same vectors."""
+import os
+import re
+import subprocess
+
+import pytest
+
+import fieldref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multilinear-map-cryptography_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+
+field = pytest.mark.parametrize("field", list(ref.FIELDS))
+
+
+# ------------------------------------------------------------------ (a) the header's constants
+def header_constants(cfg):
+    with open(os.path.join(CSRC, "bn254.hpp")) as f:
+        src = f.read()
+    body = re.search(r"struct %s \{(.*?)\n\};" % cfg, src, re.S).group(1)
+    out = {}
+    for name, limbs in re.findall(r"static constexpr u32 (\w+)\[8\] = \{(.*?)\};", body, re.S):
+        words = [int(w.rstrip("u"), 16) for w in re.findall(r"0x[0-9a-fA-F]+u?", limbs)]
+        assert len(words) == 8, (cfg, name)
+        out[name] = ref.from_limbs(words)
+    out["INV"] = int(re.search(r"static constexpr u32 INV = (0x[0-9a-fA-F]+)u;", body).group(1), 16)
+    return out
+
+
+@pytest.mark.parametrize("cfg,field", [("FrCfg", "fr"), ("FqCfg", "fq")])
+def test_header_constants_equal_the_derived_ones(cfg, field):
+    f, h = ref.BY_NAME[field], header_constants(cfg)
+    assert sorted(h) == ["INV", "M", "M2", "ONE", "R2", "R3"]
+    want = {"M": f.M, "ONE": f.ONE, "R2": f.R2, "R3": f.R3, "M2": f.M2, "INV": f.INV32}
+    for name in want:
+        assert h[name] == want[name], "%s::%s = %s, derived %s" % (cfg, name, ref.hexs(h[name]), ref.hexs(want[name]))
+    assert 4 * f.M < ref.R and f.M2 < 1 << 255  # what the lazy domain and sqr_lazy_dev assume
+
+
+# ------------------------------------------------------------------ (b) the promised ranges hold
+@field
+def test_operand_sets_cover_the_edges(field):
+    f = ref.BY_NAME[field]
+    e = ref.edge_values(f.M)
+    for v in (0, f.M - 1, f.M, f.M + 1, f.M2 - 1, f.ONE, f.R2, f.ONE + f.M, (1 << 224) - 1, (1 << 254) + 1):
+        assert v in e
+    ones = ref.all_ones_value(f.M)
+    assert ones < f.M2 <= ones + (1 << 224) and ones % (1 << 224) == (1 << 224) - 1
+    assert len(ref.unary_cases(field, f.M2)) == len([x for x in e if x < f.M2]) + 256
+    n_edges = len([x for x in e if x < f.M2])
+    assert len(ref.binary_cases(field, f.M2)) == n_edges ** 2 + 4096
+    assert len(ref.binary_cases(field, f.M2, True)) == (n_edges + 1) ** 2 + 4096
+    assert len(ref.quad_cases(field)) == 10 ** 4 + 4096
+    assert all(x < f.M for x in ref.unary_cases(field, f.M))  # inv_binary_dev never sees M
+
+
+@field
+def test_lazy_products_stay_in_range(field):
+    """mul_lazy_dev / sqr_lazy_dev: inputs < 2M (<= 2M for Fr, mle.hip) give (a b + m M) / R < 2M."""
+    f = ref.BY_NAME[field]
+    closed = field == "fr"
+    pairs = ref.binary_cases(field, f.M2, closed)
+    checked = 0
+    for a, b in pairs:
+        t = f.mul_lazy_exact(a, b)
+        assert t < f.M2 and t % f.M == f.mont_mul(a, b), (ref.hexs(a), ref.hexs(b))
+        checked += 1
+    for a in ref.unary_cases(field, f.M2, closed):
+        assert f.mul_lazy_exact(a, a) < f.M2
+        checked += 1
+    assert checked == len(pairs) + len(ref.unary_cases(field, f.M2, closed))
+
+
+@field
+def test_mul2_stays_in_range(field):
+    """mul2_lazy_dev: (a b + c d + m M) / R < 2.51 M < 4M, so one subtraction of 2M lands in [0, 2M);
+    the core quadruples include the largest T = a b + c d of the domain."""
+    f = ref.BY_NAME[field]
+    quads = ref.quad_cases(field)
+    bound = f.M + 8 * f.M * f.M // ref.R + 1  # (8 M^2 + R M) / R
+    assert bound < 4 * f.M and bound * 100 < 252 * f.M
+    worst, checked = 0, 0
+    for q in quads:
+        t = f.mul2_presub_exact(*q)
+        assert t < bound and t % f.M == f.mont_mul2(*q), [ref.hexs(v) for v in q]
+        assert (t - f.M2 if t >= f.M2 else t) < f.M2
+        worst = max(worst, t)
+        checked += 1
+    assert checked == len(quads)
+    top = (f.M2 - 1,) * 4  # T = 2 (2M - 1)^2: the largest sum of two products the domain allows
+    assert top in quads and worst >= f.M2  # (and results >= 2M, which take the subtraction, occur)
+
+
+def test_point_cases_reach_both_zeros():
+    """The equal-point cases make the differences P and R come out as 0 and as M."""
+    f = ref.FQ
+    for mixed in (True, False):
+        cs = ref.add_cases(ref.LAZY, mixed)
+        zero = [(P, R) for P, R in ref.branch_differences(cs, mixed) if P % f.M == 0 and R % f.M == 0]
+        assert {P for P, R in zero} == {0, f.M} and {R for P, R in zero} == {0, f.M}
+        assert all(c < f.M2 for p, q, w in cs for c in p + q)
+    for chain in ref.madd_chain_cases():
+        assert len(chain[1]) == len(chain[2]) == ref.MADD_CHAIN_STEPS
+    for A in [A for k, A in ref.g1_points()]:
+        assert ref.po.g1_is_on_curve(A)
+        for lam in ref.lambdas():
+            assert ref.xyzz_to_affine(ref.xyzz_of(A, lam, 0b1010)) == A
+
+
+# ------------------------------------------------------------------ (c) the host twins
+def h64(v):
+    return "%064x" % v
+
+
+@pytest.fixture(scope="module")
+def host_exe(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("hostfield") / "host_field_vectors"
+    subprocess.check_call([HIPCC, "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only",
+                           "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "host_field_vectors.cpp"), "-o", str(exe)])
+    return exe
+
+
+def run_host(exe, tmp_path, lines):
+    path = tmp_path / "vectors.txt"
+    path.write_text("".join(" ".join([op, fld] + [h64(v) for v in args]) + "\n" for op, fld, args in lines))
+    out = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stderr[-2000:])
+    rows = out.stdout.splitlines()
+    assert len(rows) == len(lines)
+    return [tuple(int(w, 16) for w in r.split()) for r in rows]
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@field
+def test_host_field_twins(host_exe, tmp_path, field):
+    """mul_cios, mul_cios64, add, sub, neg, reduce_once and inv_binary_host (which reduces inputs in
+    [M, 2M)) on the canonical-domain vectors of the device tests."""
+    f = ref.BY_NAME[field]
+    lines, want = [], []
+    for a, b in ref.binary_cases(field, f.M):
+        for op, w in (("mul_cios", f.mont_mul(a, b)), ("mul_cios64", f.mont_mul(a, b)), ("add", f.add(a, b)),
+                      ("sub", f.sub(a, b))):
+            lines.append((op, field, (a, b)))
+            want.append((w,))
+    for a in ref.unary_cases(field, f.M):
+        lines.append(("neg", field, (a,)))
+        want.append((f.neg(a),))
+    for a in ref.unary_cases(field, f.M2):
+        lines += [("reduce_once", field, (a,)), ("inv_binary_host", field, (a,))]
+        want += [(a % f.M,), (f.mont_inv(a % f.M),)]
+    got = run_host(host_exe, tmp_path, lines)
+    checked = 0
+    for (op, _, args), g, w in zip(lines, got, want):
+        assert g == w, "%s(%s) = %s, want %s" % (op, ", ".join(map(ref.hexs, args)), ref.hexs(g[0]), ref.hexs(w[0]))
+        checked += 1
+    assert checked == len(lines)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_host_point_twins(host_exe, tmp_path):
+    """Host xyzz_add / xyzz_madd / xyzz_dbl on the canonical point cases of the device tests."""
+    f = ref.FQ
+    lines, want = [], []
+    for op, mixed in (("xyzz_add", False), ("xyzz_madd", True)):
+        for p, q, w in ref.add_cases(ref.CANON, mixed):
+            lines.append((op, "fq", p + q))
+            want.append(w)
+    for p, w in ref.dbl_cases(ref.CANON):
+        lines.append(("xyzz_dbl", "fq", p))
+        want.append(w)
+    got = run_host(host_exe, tmp_path, lines)
+    checked = 0
+    for (op, _, args), P, w in zip(lines, got, want):
+        tag = "%s(%s)" % (op, ", ".join(map(ref.hexs, args)))
+        assert len(P) == 4 and all(c < f.M for c in P), tag
+        assert ref.xyzz_is_inf(P) == (w is None), tag
+        if w is not None:
+            assert ref.xyzz_to_affine(P) == w, tag
+        checked += 1
+    assert checked == len(lines)

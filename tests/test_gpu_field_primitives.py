@@ -1,0 +1,468 @@
+"""The device field and point primitives, one primitive and one operand at a time, against big
+integers (tests/fieldref.py): the Montgomery products of mont_mul.inc, the carry chains of
+field_asm.inc (build `asm`) and field_bi.inc (build `bi`, -DTNS_FIELD_BI), the lazy [0, 2M) domain
+on top of them and the XYZZ point formulas of bn254.hpp / group_ntt.hpp.  tests/device/fieldprobe.hip
+wraps each shipped function in a one-thread-a-case kernel; nothing is re-implemented on the device.
+
+Two kinds of error that proofs on random data do not show are constructed here: operand edges
+(carries through all eight limbs, values in [M, 2M), zero represented as M, 2M - 0, mul2_lazy_dev
+at its bound) and usage shapes (loop-carried and aliased operands, the node-finish loop in which
+hipcc once gave an early-clobber asm output the register of a live input).  All
+comparisons are integer-exact, and every test checks as many cases as were generated."""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import fieldref as ref
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "multilinear-map-cryptography_amd")
+BUILDS = {"asm": "libtns_fieldprobe.so", "bi": "libtns_fieldprobe_bi.so"}
+FIELD_ID = {"fr": 0, "fq": 1}
+
+# the op numbers of fieldprobe.hip's enum, in its order
+OPS = ("F_MUL F_SQR F_ADD F_SUB F_NEG F_REDUCE_ONCE F_TO_MONT F_FROM_MONT F_INV F_INV_WINDOW F_INV_BINARY "
+       "F_MUL_LAZY F_SQR_LAZY F_MUL2_LAZY F_ADD2 F_SUB2 F_CMINUS_2M F_CMINUS_M F_REDUCE_2M F_CANON2 "
+       "F_ZERO_LAZY F_SQRT "
+       "P_MUL_AB P_MUL_BA P_SQR P_MUL_LAZY_AB P_MUL_LAZY_BA P_SQR_LAZY P_ADD2_SELF P_SUB_BA P_CHAIN_GLOBAL "
+       "P_FINISH2 P_ALIAS "
+       "G_MADD_LAZY G_ADD_LAZY G_DBL_LAZY G_CANON G_MUL_CANON G_ADD G_MADD G_DBL G_MDBL G_MADD_CHAIN").split()
+OP = {name: i for i, name in enumerate(OPS)}
+ITERS = 33
+HIP_ERRORS = []  # a failed launch ends the file's GPU work: nothing more runs on a device that faulted
+
+build = pytest.mark.parametrize("build", list(BUILDS))
+field = pytest.mark.parametrize("field", list(ref.FIELDS))
+
+
+@functools.lru_cache(maxsize=None)
+def probe(build):
+    path = os.path.join(PKG, BUILDS[build])
+    assert os.path.exists(path), "build() builds " + BUILDS[build]
+    lib = C.CDLL(path)
+    lib.fieldprobe_run.restype = C.c_int
+    lib.fieldprobe_run.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
+    for f in (lib.fieldprobe_in_words, lib.fieldprobe_out_words):
+        f.restype, f.argtypes = C.c_int, [C.c_int, C.c_int]
+    assert lib.fieldprobe_op_count() == len(OPS)
+    return lib
+
+
+def run(build, field, op, cases, iters=0):
+    """cases: one tuple of 256-bit ints a case.  Returns one tuple of 256-bit ints a case."""
+    lib = probe(build)
+    n = len(cases)
+    win, wout = lib.fieldprobe_in_words(OP[op], iters), lib.fieldprobe_out_words(OP[op], iters)
+    assert all(len(c) * 8 == win for c in cases), (op, win)
+    if op == "F_INV_BINARY":  # the Euclid loop does not terminate on M: never send it
+        assert all(0 <= c[0] < ref.MODULI[field] for c in cases)
+    raw = b"".join(v.to_bytes(32, "little") for c in cases for v in c)
+    src = np.frombuffer(raw, dtype=np.uint32).copy()
+    dst = np.zeros(n * wout, dtype=np.uint32)
+    assert src.size == n * win
+    assert not HIP_ERRORS, "an earlier probe call failed (%s): no further GPU work in this process" % HIP_ERRORS[0]
+    st = lib.fieldprobe_run(OP[op], FIELD_ID[field], src.ctypes.data, src.size, dst.ctypes.data, dst.size, n, iters)
+    if st != 0:
+        HIP_ERRORS.append("%s/%s/%s: fieldprobe_run returned %d" % (build, field, op, st))
+    assert st == 0, HIP_ERRORS[-1]
+    out = dst.tobytes()
+    k = wout // 8
+    vals = [int.from_bytes(out[32 * i:32 * i + 32], "little") for i in range(n * k)]
+    return [tuple(vals[i * k:(i + 1) * k]) for i in range(n)]
+
+
+def hx(vals):
+    return "(" + ", ".join(ref.hexs(v) for v in vals) + ")"
+
+
+def check_exact(what, cases, got, want):
+    """got == want limb for limb, on every case."""
+    assert len(got) == len(cases) == len(want)
+    checked = 0
+    for c, g, w in zip(cases, got, want):
+        w = w if isinstance(w, tuple) else (w,)
+        assert g == w, "%s%s = %s, want %s" % (what, hx(c), hx(g), hx(w))
+        checked += 1
+    assert checked == len(cases)
+
+
+def check_lazy(what, cases, got, want, M, closed=False, exact=None):
+    """got in the promised range ([0, 2M), or [0, 2M] for the closed Fr domain), got = want mod M,
+    and got equal to the exact integer the function forms where one is given."""
+    assert len(got) == len(cases) == len(want)
+    checked = 0
+    for i, (c, g, w) in enumerate(zip(cases, got, want)):
+        (g,) = g
+        assert g < 2 * M or (closed and g == 2 * M), "%s%s = %s: outside the lazy domain" % (what, hx(c), ref.hexs(g))
+        assert g % M == w, "%s%s = %s, want %s (mod M)" % (what, hx(c), ref.hexs(g), ref.hexs(w))
+        if exact is not None:
+            assert g == exact[i], "%s%s = %s, want exactly %s" % (what, hx(c), ref.hexs(g), ref.hexs(exact[i]))
+        checked += 1
+    assert checked == len(cases)
+
+
+def unary(field, hi, closed=False):
+    return [(x,) for x in ref.unary_cases(field, hi, closed)]
+
+
+# ------------------------------------------------------------------ expected values, shared by builds
+@functools.lru_cache(maxsize=None)
+def want_binary(field, hi, closed, fn):
+    f = ref.BY_NAME[field]
+    return [getattr(f, fn)(a % f.M, b % f.M) for a, b in ref.binary_cases(field, hi, closed)]
+
+
+@functools.lru_cache(maxsize=None)
+def want_mul_lazy_exact(field, closed):
+    f = ref.BY_NAME[field]
+    return [f.mul_lazy_exact(a, b) for a, b in ref.binary_cases(field, f.M2, closed)]
+
+
+@functools.lru_cache(maxsize=None)
+def want_mul2(field):
+    f = ref.BY_NAME[field]
+    want, exact, subtracted = [], [], 0
+    for q in ref.quad_cases(field):
+        t = f.mul2_presub_exact(*q)
+        want.append(f.mont_mul2(*q))
+        exact.append(t - f.M2 if t >= f.M2 else t)
+        subtracted += t >= f.M2
+    return want, exact, subtracted
+
+
+@functools.lru_cache(maxsize=None)
+def want_inverse(field, hi):
+    f = ref.BY_NAME[field]
+    return [f.mont_inv(a % f.M) for a in ref.unary_cases(field, hi)]
+
+
+# ------------------------------------------------------------------ canonical functions
+@build
+@field
+def test_mul_sqr(build, field):
+    f = ref.BY_NAME[field]
+    pairs = ref.binary_cases(field, f.M)
+    check_exact("mul", pairs, run(build, field, "F_MUL", pairs), want_binary(field, f.M, False, "mont_mul"))
+    xs = unary(field, f.M)
+    check_exact("sqr", xs, run(build, field, "F_SQR", xs), [f.mont_mul(a, a) for a, in xs])
+
+
+@build
+@field
+def test_to_mont_from_mont(build, field):
+    f = ref.BY_NAME[field]
+    xs = unary(field, f.M)
+    check_exact("to_mont", xs, run(build, field, "F_TO_MONT", xs), [f.to_mont(a) for a, in xs])
+    check_exact("from_mont", xs, run(build, field, "F_FROM_MONT", xs), [f.from_mont(a) for a, in xs])
+
+
+@build
+@field
+def test_add_sub_neg(build, field):
+    f = ref.BY_NAME[field]
+    pairs = ref.binary_cases(field, f.M)
+    check_exact("add", pairs, run(build, field, "F_ADD", pairs), want_binary(field, f.M, False, "add"))
+    check_exact("sub", pairs, run(build, field, "F_SUB", pairs), want_binary(field, f.M, False, "sub"))
+    xs = unary(field, f.M)
+    check_exact("neg", xs, run(build, field, "F_NEG", xs), [f.neg(a) for a, in xs])
+
+
+@build
+@field
+def test_reduce_once(build, field):
+    """reduce_once: [0, 2M) -> [0, M); twice (mle.hip sc_canon): [0, 2M] -> [0, M), for Fr."""
+    f = ref.BY_NAME[field]
+    xs = unary(field, f.M2)
+    assert (f.M,) in xs and (f.M2 - 1,) in xs
+    check_exact("reduce_once", xs, run(build, field, "F_REDUCE_ONCE", xs), [a % f.M for a, in xs])
+    xs = unary(field, f.M2, closed=field == "fr")
+    assert ((f.M2,) in xs) == (field == "fr")
+    check_exact("sc_canon", xs, run(build, field, "F_CANON2", xs), [a % f.M for a, in xs])
+
+
+@build
+@field
+def test_inverse(build, field):
+    """inv (Fermat chain) on [0, M), inv(0) = 0; inv_window_dev also on [M, 2M)."""
+    f = ref.BY_NAME[field]
+    xs = unary(field, f.M)
+    assert (0,) in xs
+    check_exact("inv", xs, run(build, field, "F_INV", xs), want_inverse(field, f.M))
+    xs = unary(field, f.M2)
+    assert sum(a >= f.M for a, in xs) > 100
+    check_exact("inv_window_dev", xs, run(build, field, "F_INV_WINDOW", xs), want_inverse(field, f.M2))
+
+
+@build
+@field
+def test_inv_binary(build, field):
+    """inv_binary_dev on 0 and 1 .. M-1 only: a >= M is outside its domain (it would not return)."""
+    f = ref.BY_NAME[field]
+    xs = unary(field, f.M)
+    assert (0,) in xs and (1,) in xs and (f.M - 1,) in xs and all(a < f.M for a, in xs)
+    check_exact("inv_binary_dev", xs, run(build, field, "F_INV_BINARY", xs), want_inverse(field, f.M))
+
+
+@build
+def test_fq_sqrt_candidate(build):
+    f = ref.FQ
+    xs = [(a,) for a in ref.sqrt_cases()]
+    want = [f.mont_sqrt_candidate(a) for a, in xs]
+    assert sum(f.mont_mul(w, w) == a for (a,), w in zip(xs, want)) >= 64  # squares ...
+    assert sum(f.mont_mul(w, w) != a for (a,), w in zip(xs, want)) >= 16  # ... and non-squares
+    check_exact("fq_sqrt_candidate_dev", xs, run(build, "fq", "F_SQRT", xs), want)
+
+
+# ------------------------------------------------------------------ lazy functions
+@build
+@field
+def test_mul_sqr_lazy(build, field):
+    f = ref.BY_NAME[field]
+    closed = field == "fr"  # mle.hip: inputs <= 2M give results < 2M
+    pairs = ref.binary_cases(field, f.M2, closed)
+    assert ((f.M2, f.M2) in pairs) == closed
+    check_lazy("mul_lazy_dev", pairs, run(build, field, "F_MUL_LAZY", pairs),
+               want_binary(field, f.M2, closed, "mont_mul"), f.M, exact=want_mul_lazy_exact(field, closed))
+    xs = unary(field, f.M2, closed)
+    check_lazy("sqr_lazy_dev", xs, run(build, field, "F_SQR_LAZY", xs), [f.mont_mul(a % f.M, a % f.M) for a, in xs],
+               f.M, exact=[f.mul_lazy_exact(a, a) for a, in xs])
+
+
+@build
+@field
+def test_mul2_lazy(build, field):
+    """Mont(a b + c d) with one subtraction of 2M, the core {0, .., 2M-1}^4 reaching its bound."""
+    f = ref.BY_NAME[field]
+    quads = ref.quad_cases(field)
+    want, exact, subtracted = want_mul2(field)
+    assert subtracted > 0 and (f.M2 - 1,) * 4 in quads  # the subtraction of 2M is exercised
+    check_lazy("mul2_lazy_dev", quads, run(build, field, "F_MUL2_LAZY", quads), want, f.M, exact=exact)
+
+
+@build
+@field
+def test_add2_sub2(build, field):
+    f = ref.BY_NAME[field]
+    closed = field == "fr"
+    pairs = ref.binary_cases(field, f.M2, closed)
+    check_lazy("add2_dev", pairs, run(build, field, "F_ADD2", pairs), want_binary(field, f.M2, closed, "add"), f.M,
+               closed, exact=[a + b - (f.M2 if a + b >= f.M2 else 0) for a, b in pairs])
+    check_lazy("sub2_dev", pairs, run(build, field, "F_SUB2", pairs), want_binary(field, f.M2, closed, "sub"), f.M,
+               closed, exact=[a - b + (f.M2 if a < b else 0) for a, b in pairs])
+
+
+@build
+@field
+def test_const_minus_reduce_2m(build, field):
+    """K - a (K = 2M on [0, 2M), the closed [0, 2M] for Fr; K = M on [0, M]) and the conditional
+    subtraction of 2M on [0, 4M).  2M - 0 is 2M itself: the one result outside [0, 2M)."""
+    f = ref.BY_NAME[field]
+    closed = field == "fr"
+    xs = unary(field, f.M2, closed)
+    assert (0,) in xs
+    got = run(build, field, "F_CMINUS_2M", xs)
+    check_lazy("const_minus_dev<2M>", xs, got, [f.neg(a % f.M) for a, in xs], f.M, closed=True,
+               exact=[f.M2 - a for a, in xs])
+    assert all((g == f.M2) == (a == 0) for (a,), (g,) in zip(xs, got))
+    xs = unary(field, f.M, closed=True)
+    check_lazy("const_minus_dev<M>", xs, run(build, field, "F_CMINUS_M", xs), [f.neg(a % f.M) for a, in xs], f.M,
+               exact=[f.M - a for a, in xs])
+    xs = unary(field, 4 * f.M, closed)
+    check_lazy("reduce_once_2m_dev", xs, run(build, field, "F_REDUCE_2M", xs), [a % f.M for a, in xs], f.M, closed,
+               exact=[a - f.M2 if a >= f.M2 else a for a, in xs])
+
+
+@build
+def test_fq_zero_lazy(build):
+    """True exactly for 0 and M, over every edge value and 256 draws from [0, 2^256)."""
+    f = ref.FQ
+    xs = unary("fq", ref.R)
+    assert (0,) in xs and (f.M,) in xs and (f.M + 1,) in xs and (f.M2 - 1,) in xs and any(a >= 1 << 255 for a, in xs)
+    check_exact("fq_zero_lazy", xs, run(build, "fq", "F_ZERO_LAZY", xs), [int(a in (0, f.M)) for a, in xs])
+
+
+# ------------------------------------------------------------------ usage patterns
+def pattern_operands(field):
+    f = ref.BY_NAME[field]
+    rng = ref._rng(field, "pattern")
+    fixed = [(f.ONE, f.M - 1), (f.M - 1, f.M - 1), (f.R2, f.ONE), (ref.all_ones_value(f.M) % f.M, f.M - 2), (2, 3)]
+    return fixed + [(rng.randrange(f.M), rng.randrange(f.M)) for _ in range(59)]
+
+
+def iterate(step, a, n=ITERS):
+    out = []
+    for _ in range(n):
+        a = step(a)
+        out.append(a)
+    return tuple(out)
+
+
+@build
+@field
+def test_loop_carried_products(build, field):
+    """a = mul(a, b), a = mul(b, a), a = sqr(a) and their lazy forms, 33 steps, every iterate."""
+    f = ref.BY_NAME[field]
+    ab = pattern_operands(field)
+    want = [iterate(lambda x: f.mont_mul(x, b), a) for a, b in ab]
+    check_exact("a = mul(a, b) x33", ab, run(build, field, "P_MUL_AB", ab, ITERS), want)
+    check_exact("a = mul(b, a) x33", ab, run(build, field, "P_MUL_BA", ab, ITERS), want)
+    aa = [(a,) for a, b in ab]
+    check_exact("a = sqr(a) x33", aa, run(build, field, "P_SQR", aa, ITERS),
+                [iterate(lambda x: f.mont_mul(x, x), a) for a, in aa])
+    lazy = [(a + f.M * (i & 1), b + f.M * ((i >> 1) & 1)) for i, (a, b) in enumerate(ab)]
+    want = [iterate(lambda x: f.mul_lazy_exact(x, b), a) for a, b in lazy]
+    assert all(x < f.M2 for w in want for x in w)
+    check_exact("a = mul_lazy_dev(a, b) x33", lazy, run(build, field, "P_MUL_LAZY_AB", lazy, ITERS), want)
+    check_exact("a = mul_lazy_dev(b, a) x33", lazy, run(build, field, "P_MUL_LAZY_BA", lazy, ITERS), want)
+    aa = [(a,) for a, b in lazy]
+    check_exact("a = sqr_lazy_dev(a) x33", aa, run(build, field, "P_SQR_LAZY", aa, ITERS),
+                [iterate(lambda x: f.mul_lazy_exact(x, x), a) for a, in aa])
+
+
+@build
+@field
+def test_chain_through_memory(build, field):
+    """iv = mul(iv, d[j]), d[j] loaded and iv stored every step; and the node-finish loop of
+    lagrange.hip, inv_j = mul(iv, pre[j]); iv = mul(iv, d[j]) -- the shape whose asm once
+    overwrote a live input."""
+    f = ref.BY_NAME[field]
+    rng = ref._rng(field, "chain")
+    cases, want = [], []
+    for _ in range(64):
+        c = tuple(rng.randrange(f.M) for _ in range(1 + ITERS))
+        iv, w = c[0], []
+        for d in c[1:]:
+            iv = f.mont_mul(iv, d)
+            w.append(iv)
+        cases.append(c)
+        want.append(tuple(w))
+    check_exact("iv = mul(iv, d[j])", cases, run(build, field, "P_CHAIN_GLOBAL", cases, ITERS), want)
+    cases, want = [], []
+    for _ in range(64):
+        c = tuple(rng.randrange(f.M) for _ in range(1 + 2 * ITERS))
+        iv, w = c[0], []
+        for j in range(ITERS):
+            w.append(f.mont_mul(iv, c[1 + 2 * j]))
+            iv = f.mont_mul(iv, c[2 + 2 * j])
+            w.append(iv)
+        cases.append(c)
+        want.append(tuple(w))
+    check_exact("inv_j = mul(iv, pre[j]); iv = mul(iv, d[j])", cases, run(build, field, "P_FINISH2", cases, ITERS), want)
+
+
+@build
+@field
+def test_aliased_operands(build, field):
+    """mul(a, a), mul_lazy_dev(a, a), mul2_lazy_dev(a, a, a, a), mul2_lazy_dev(a, b, b, a),
+    add(a, a), sub(a, a), sub2_dev(a, a) over every edge value of [0, M)."""
+    f = ref.BY_NAME[field]
+    xs = ref.unary_cases(field, f.M)
+    ab = [(a, xs[(5 * i + 1) % len(xs)]) for i, a in enumerate(xs)]
+
+    def red2m(t):
+        return t - f.M2 if t >= f.M2 else t
+
+    want = [(f.mont_mul(a, a), f.mul_lazy_exact(a, a), red2m(f.mul2_presub_exact(a, a, a, a)),
+             red2m(f.mul2_presub_exact(a, b, b, a)), f.add(a, a), 0, 0) for a, b in ab]
+    check_exact("aliased (mul, mul_lazy, mul2 aaaa, mul2 abba, add, sub, sub2)", ab, run(build, field, "P_ALIAS", ab), want)
+
+
+@build
+@field
+def test_loop_carried_carry_chains(build, field):
+    """In place a = add2_dev(a, a) (from [0, 2M)) and a = sub(b, a) (canonical), 33 steps."""
+    f = ref.BY_NAME[field]
+    xs = unary(field, f.M2)
+    check_exact("a = add2_dev(a, a) x33", xs, run(build, field, "P_ADD2_SELF", xs, ITERS),
+                [iterate(lambda x: 2 * x - (f.M2 if 2 * x >= f.M2 else 0), a) for a, in xs])
+    ab = list(ref.binary_cases(field, f.M)[::37])
+    check_exact("a = sub(b, a) x33", ab, run(build, field, "P_SUB_BA", ab, ITERS),
+                [iterate(lambda x: f.sub(b, x), a) for a, b in ab])
+
+
+# ------------------------------------------------------------------ point formulas
+def flat(*parts):
+    out = []
+    for p in parts:
+        out += list(p) if isinstance(p, tuple) else [p]
+    return tuple(out)
+
+
+def check_points(what, cases, got, want, canonical):
+    """Every coordinate below 2M (below M where the function returns canonical values), zz^3 = zzz^2
+    on every finite result, identity <=> zz in {0, M}, and the affine value equal to the reference."""
+    f = ref.FQ
+    assert len(got) == len(cases) == len(want)
+    checked = 0
+    for c, g, w in zip(cases, got, want):
+        for k in range(0, len(g), 4):  # (a chain returns every partial sum)
+            P, A = g[k:k + 4], (w[k // 4] if isinstance(w, tuple) and len(g) > 4 else w)
+            tag = "%s%s -> %s" % (what, hx(c), hx(P))
+            assert all(v < (f.M if canonical else f.M2) for v in P), tag + ": coordinate out of range"
+            assert ref.xyzz_is_inf(P) == (A is None), tag + ": identity mismatch, want %s" % (A,)
+            if A is not None:
+                zz, zzz = f.from_mont(P[2] % f.M), f.from_mont(P[3] % f.M)
+                assert pow(zz, 3, f.M) == zzz * zzz % f.M, tag + ": zz^3 != zzz^2"
+                assert ref.xyzz_to_affine(P) == A, tag + ": affine %s, want %s" % (ref.xyzz_to_affine(P), A)
+        checked += 1
+    assert checked == len(cases)
+
+
+@build
+@pytest.mark.parametrize("op,mixed", [("G_MADD_LAZY", True), ("G_ADD_LAZY", False)])
+def test_lazy_point_addition(build, op, mixed):
+    """xyzz_madd_lazy / xyzz_add_lazy: generic sums, the doubling branch reached with P and R
+    coming out both as 0 and as M, opposite points, identities as zz = 0 and zz = M."""
+    f = ref.FQ
+    cs = ref.add_cases(ref.LAZY, mixed)
+    zero = [(P, R) for P, R in ref.branch_differences(cs, mixed) if P % f.M == 0 and R % f.M == 0]
+    assert {0, f.M} <= {P for P, R in zero} and {0, f.M} <= {R for P, R in zero}
+    cases = [flat(p, q) for p, q, w in cs]
+    check_points(op, cases, run(build, "fq", op, cases), [w for p, q, w in cs], canonical=False)
+
+
+@build
+def test_lazy_doubling_and_canon(build):
+    f = ref.FQ
+    cs = ref.dbl_cases(ref.LAZY)
+    cases = [flat(p) for p, w in cs]
+    check_points("xyzz_dbl_lazy", cases, run(build, "fq", "G_DBL_LAZY", cases), [w for p, w in cs], canonical=False)
+    cases = [flat(p) for p in ref.canon_cases()]
+    check_exact("xyzz_canon", cases, run(build, "fq", "G_CANON", cases), [tuple(v % f.M for v in p) for p in cases])
+
+
+@build
+def test_scalar_multiplication(build):
+    """xyzz_mul_canon: k in {0, 1, 2, r-1, 2^32-1, 2^32, 2^64, 2^224} and random k, results canonical."""
+    cs = ref.mul_cases()
+    cases = [flat(p, k) for p, k, w in cs]
+    check_points("xyzz_mul_canon", cases, run(build, "fq", "G_MUL_CANON", cases), [w for p, k, w in cs], canonical=True)
+
+
+@build
+def test_madd_chain(build):
+    """16 steps of acc = xyzz_madd_lazy(acc, q[j]) through copy, doubling, generic, cancelling and
+    identity steps, every partial sum checked."""
+    cs = ref.madd_chain_cases()
+    cases = [flat(acc, *qs) for acc, qs, sums in cs]
+    got = run(build, "fq", "G_MADD_CHAIN", cases, ref.MADD_CHAIN_STEPS)
+    check_points("madd chain", cases, got, [sums for acc, qs, sums in cs], canonical=False)
+
+
+@build
+def test_canonical_point_formulas(build):
+    """xyzz_add / xyzz_madd / xyzz_dbl / xyzz_mdbl as compiled for the device, canonical operands."""
+    for op, mixed in (("G_ADD", False), ("G_MADD", True)):
+        cs = ref.add_cases(ref.CANON, mixed)
+        cases = [flat(p, q) for p, q, w in cs]
+        check_points(op, cases, run(build, "fq", op, cases), [w for p, q, w in cs], canonical=True)
+    cs = ref.dbl_cases(ref.CANON)
+    cases = [flat(p) for p, w in cs]
+    check_points("xyzz_dbl", cases, run(build, "fq", "G_DBL", cases), [w for p, w in cs], canonical=True)
+    cs = ref.mdbl_cases()
+    cases = [flat(a) for a, w in cs]
+    check_points("xyzz_mdbl", cases, run(build, "fq", "G_MDBL", cases), [w for a, w in cs], canonical=True)
