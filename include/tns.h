@@ -372,6 +372,49 @@ int tns_kzg_verify(const tns_vk *vk, const uint64_t commitment_proj[12], const u
  * arrays of n entries (commitments/proofs uint64_t[12] each, points/values uint64_t[4]). */
 int tns_kzg_batch_verify(const tns_vk *vk, size_t n, const uint64_t *commitments_proj, const uint64_t *points,
                          const uint64_t *values, const uint64_t *proofs_proj, int *ok);
+/* ---- many openings in one sound check (kzg_verify.hip)
+ * tns_kzg_batch_verify above keeps the reference's equation and its public challenges; the three
+ * calls below check k openings (C_i, z_i, v_i, pi_i) soundly, on the device except for two pairings:
+ *   L = sum g_i C_i - (sum g_i v_i) G + sum (g_i z_i) pi_i,   R = sum g_i pi_i,
+ *   *ok = 1  iff  e(L, G2) == e(R, tau G2),
+ * the openings' own equations e(C_i - v_i G + z_i pi_i, G2) == e(pi_i, tau G2) added up under the
+ * weights g_i.  Valid openings always pass.  With an invalid one the check passes for a fraction of
+ * about 2^-128 of the challenges only, PROVIDED they are not known to whoever made the proofs: pass
+ * seed == NULL (32 bytes drawn from the OS) unless the seed is chosen after the proofs and kept from
+ * their author; a fixed public seed checks nothing against an adversary.  g_i is the i-th 128-bit
+ * little-endian integer of ChaCha20Rng::from_seed(seed)'s word stream (block i / 4, 64-bit counter
+ * from 0, stream 0: tns_fr_rand_batch's generator without the rejection loop), 0 replaced by 1;
+ * tns_verify_challenges returns them.
+ * Points are untrusted affine uint64_t[8] Montgomery limbs (tns_vc_open_all's encoding, identity =
+ * all zeros): before any MSM each must have both coordinates below the modulus and lie on the curve.
+ * A malformed point is a failed verification, not an error: TNS_OK, *ok = 0, *bad_index = the lowest
+ * malformed position.  Fr inputs are taken as reduced.
+ * bad_index may be NULL; it is written only when *ok == 0.  When the batch fails and it is not
+ * NULL, the batch is bisected with the same challenges down to the lowest failing index (up to the
+ * 2^-128 bound; the last, single-opening check is exact): about the MSM work of one more full
+ * check and at most ceil(log2 k) + 1 more pairing checks.
+ * Errors: a NULL ctx, vk, ok or required array -> TNS_ERR_INVALID_PARAMETERS; n_commitments not 1
+ * or k (k > 0) -> TNS_ERR_COMMITMENT ("Batch verify input lengths must match"); a failed device
+ * allocation -> TNS_ERR_OOM.  Nothing is written on error.  No SRS is involved and nothing is kept
+ * on the context: the uploaded inputs and 64 bytes of device scratch an opening (96 with one
+ * commitment per opening) live during the call.
+ *
+ * k openings.  commitments_affine: n_commitments points, n_commitments == k (one per opening) or 1
+ * (shared by all).  points/values: k Fr; proofs_affine: k points.  k == 0 -> *ok = 1. */
+int tns_kzg_verify_many(tns_ctx *ctx, const tns_vk *vk, const uint64_t *commitments_affine, size_t n_commitments,
+                        const uint64_t *points, const uint64_t *values, const uint64_t *proofs_affine, size_t k,
+                        const uint8_t seed[32], int *ok, uint64_t *bad_index);
+/* KZGVectorCommitment::verify (src/commitments.rs:473-483) for every index at once: z_i = i, v_i = vec[i],
+ * proofs as tns_vc_open_all writes them. */
+int tns_vc_verify_all(tns_ctx *ctx, const tns_vk *vk, const uint64_t commitment_proj[12], const uint64_t *vec,
+                      size_t n, const uint64_t *proofs_affine, const uint8_t seed[32], int *ok, uint64_t *bad_index);
+/* the same on device-resident vec (n Fr) and proofs (n affine points): pairs with tns_vc_open_all_device, no PCIe */
+int tns_vc_verify_all_device(tns_ctx *ctx, const tns_vk *vk, const uint64_t commitment_proj[12], const uint64_t *d_vec,
+                             size_t n, const uint64_t *d_proofs_affine, const uint8_t seed[32], int *ok,
+                             uint64_t *bad_index);
+/* host utility (no device): challenges [first, first + count) of `seed` as canonical uint64_t[4] each, so that
+ * another verifier can reproduce the check */
+void tns_verify_challenges(const uint8_t seed[32], uint64_t first, size_t count, uint64_t *out_canonical);
 /* Twist::verify / Shout::verify (src/twist.rs:255-304, src/shout.rs:225-274) on a proof of
  * tns_twist_prove / tns_shout_prove; *ok = 1 valid, 0 invalid. */
 int tns_twist_verify(const tns_vk *vk, const tns_proof *proof, int *ok);
@@ -464,7 +507,8 @@ int tns_shout_prove_sharded(tns_ctx *ctx, const tns_srs *srs, const tns_params *
 /* ---------------------------------------------------------------- kernel timing */
 /* HIP-event timing of the named stages on the context stream ("msm_accumulate",
  * "msm_sort", "msm_digits", "msm_reduce", "ntt_stage", "ntt_lds", "ntt_pointwise",
- * "interp_tile", "sumcheck_round", "open_scan"; the SRS files' "g1_decode", "g1_encode").
+ * "interp_tile", "sumcheck_round", "open_scan"; the SRS files' "g1_decode", "g1_encode"; the
+ * batched verifier's "verify_points", "verify_scalars").
  * Enabling resets the totals and the stage
  * filter of tns_profile_only (call that after enabling). */
 int tns_profile_enable(tns_ctx *ctx, int on);

@@ -107,6 +107,26 @@ void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const F
                      DevBuf &sbuf0, DevBuf &sbuf1, Comm &m, ExtraPayload *extra = nullptr,
                      const std::function<void()> &extra_ready = nullptr,
                      const std::function<void()> &side_work = nullptr);
+// abi_host.cpp: a tns_vk's three points, each checked against its curve
+struct Vk {
+  G1Affine g1;
+  G2Affine g2, g2_tau;
+};
+Vk vk_load(const tns_vk *vk);
+// kzg_verify.hip: k openings (C_i, z_i, v_i, pi_i) on the device, checked in one weighted pairing
+// equation.  commitments == nullptr: `shared` is every opening's commitment; z == nullptr: z_i = i
+// (a vector commitment's openings); v and z in Montgomery form.
+struct VerifyBatch {
+  const G1Affine *proofs = nullptr;
+  const G1Affine *commitments = nullptr;
+  G1Affine shared{};
+  const Fr *z = nullptr, *v = nullptr;
+  size_t k = 0;
+};
+// false: *bad = the lowest malformed position, or with `locate` the lowest failing opening's
+// (bisected with the same challenges); seed == nullptr: 32 bytes from the OS
+bool kzg_verify_many_dev(Ctx *c, const Vk &vk, const VerifyBatch &in, const uint8_t seed[32], bool locate,
+                         uint64_t *bad);
 // prove.hip
 void check_shard(const Comm &m, size_t N, const char *what);
 size_t slice_count(uint64_t n_total, size_t first, size_t L);

@@ -29,6 +29,25 @@ static void par_convert(const uint64_t *in, size_t n, uint64_t *out, F f) {
   for (auto &x : th) x.join();
 }
 
+static G2Affine g2_from_limbs(const uint64_t in[16]) {
+  G2Affine g;
+  std::memcpy(&g.x0, in, 32);
+  std::memcpy(&g.x1, in + 4, 32);
+  std::memcpy(&g.y0, in + 8, 32);
+  std::memcpy(&g.y1, in + 12, 32);
+  g.inf = g.x0.is_zero() && g.x1.is_zero() && g.y0.is_zero() && g.y1.is_zero();
+  if (!g.inf && !g2_on_curve(g)) throw Error(TNS_ERR_INVALID_PARAMETERS, "G2 point not on the twist");
+  return g;
+}
+static G1Affine g1_from_limbs(const uint64_t in[8]) {
+  G1Affine a;
+  std::memcpy(&a.x, in, 32);
+  std::memcpy(&a.y, in + 4, 32);
+  if (!a.is_inf() && !g1_on_curve(a)) throw Error(TNS_ERR_INVALID_PARAMETERS, "G1 point not on the curve");
+  return a;
+}
+Vk vk_load(const tns_vk *vk) { return Vk{g1_from_limbs(vk->g1), g2_from_limbs(vk->g2), g2_from_limbs(vk->g2_tau)}; }
+
 }  // namespace tns
 
 using namespace tns;
@@ -71,16 +90,6 @@ void tns_transcript_challenge_field_element(tns_transcript *t, const uint8_t *la
 }
 
 // ---------------------------------------------------------------- verifiers (host)
-static G2Affine g2_from_limbs(const uint64_t in[16]) {
-  G2Affine g;
-  std::memcpy(&g.x0, in, 32);
-  std::memcpy(&g.x1, in + 4, 32);
-  std::memcpy(&g.y0, in + 8, 32);
-  std::memcpy(&g.y1, in + 12, 32);
-  g.inf = g.x0.is_zero() && g.x1.is_zero() && g.y0.is_zero() && g.y1.is_zero();
-  if (!g.inf && !g2_on_curve(g)) throw Error(TNS_ERR_INVALID_PARAMETERS, "G2 point not on the twist");
-  return g;
-}
 static void g2_to_limbs(const G2Affine &g, uint64_t out[16]) {
   if (g.inf) {
     std::memset(out, 0, 128);
@@ -91,18 +100,6 @@ static void g2_to_limbs(const G2Affine &g, uint64_t out[16]) {
   std::memcpy(out + 8, &g.y0, 32);
   std::memcpy(out + 12, &g.y1, 32);
 }
-static G1Affine g1_from_limbs(const uint64_t in[8]) {
-  G1Affine a;
-  std::memcpy(&a.x, in, 32);
-  std::memcpy(&a.y, in + 4, 32);
-  if (!a.is_inf() && !g1_on_curve(a)) throw Error(TNS_ERR_INVALID_PARAMETERS, "G1 point not on the curve");
-  return a;
-}
-struct Vk {
-  G1Affine g1;
-  G2Affine g2, g2_tau;
-};
-static Vk vk_load(const tns_vk *vk) { return Vk{g1_from_limbs(vk->g1), g2_from_limbs(vk->g2), g2_from_limbs(vk->g2_tau)}; }
 static Fr fr_load(const uint64_t x[4]) {
   Fr r;
   std::memcpy(&r, x, 32);
@@ -399,6 +396,11 @@ int tns_comm_stats(const tns_comm *comm, double out[4]) {
 // n draws of ark-ff UniformRand for Fr from one ChaCha20Rng::from_seed(seed) stream (host)
 void tns_fr_rand_batch(const uint8_t seed[32], size_t n, uint64_t *out_mont) {
   host_fr_rand_stream(seed, n, (Fr *)out_mont);
+}
+
+// the challenges of tns_kzg_verify_many / tns_vc_verify_all (kzg_verify.hip), on the host
+void tns_verify_challenges(const uint8_t seed[32], uint64_t first, size_t count, uint64_t *out_canonical) {
+  verify_challenges_host(seed, first, count, out_canonical);
 }
 
 // ---------------------------------------------------------------- host utilities

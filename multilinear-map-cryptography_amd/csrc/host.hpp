@@ -31,6 +31,8 @@ bool kzg_verify_host(const G1Affine &g1, const G2Affine &g2, const G2Affine &g2_
                      const Fr &z, const Fr &v, const G1Affine &pi);
 bool kzg_batch_verify_host(const G1Affine &g1, const G2Affine &g2, const G2Affine &g2_tau, size_t n,
                            const G1Affine *C, const Fr *z, const Fr *v, const G1Affine *pi);
+// the batched check's challenges [first, first + count) of `seed`, canonical 4 x u64 each
+void verify_challenges_host(const uint8_t seed[32], uint64_t first, size_t count, uint64_t *out);
 bool protocol_verify_host(const G1Affine &g1, const G2Affine &g2, const G2Affine &g2_tau, const char *label0,
                           const char *label1, const G1Affine C[2], const Fr *rounds, unsigned nv,
                           const Fr &final_eval, unsigned n_openings, const G1Affine pi[2], const Fr vals[2]);

@@ -6,6 +6,7 @@
 // Restated step by step, including batch_verify's pairing equation exactly as written
 // (e(sum g_i (C_i - v_i G), G2) == e(sum g_i pi_i, sum g_i (tau - z_i) G2) with the g_i drawn
 // from ChaCha20Rng([42;32])), so that every boolean matches the reference's.
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -114,6 +115,30 @@ bool kzg_batch_verify_host(const G1Affine &g1, const G2Affine &g2, const G2Affin
   }
   const G1Xyzz left = xyzz_add(bc, g1_mul_host(g1_neg(g1), bv));
   return pairing_eq(xyzz_to_affine(left), g2, xyzz_to_affine(bp), bg2);
+}
+
+// The challenges of the sound batched check (kzg_verify.hip computes the same on the device):
+// gamma_i = the i-th 128-bit little-endian integer of ChaCha20Rng::from_seed(seed)'s word stream,
+// i.e. words 4 (i % 4) .. + 3 of block i / 4, with 0 replaced by 1; canonical, 4 x u64 each.
+void verify_challenges_host(const uint8_t seed[32], uint64_t first, size_t count, uint64_t *out) {
+  uint32_t key[8], blk[16];
+  for (int i = 0; i < 8; i++)
+    key[i] = (uint32_t)seed[4 * i] | (uint32_t)seed[4 * i + 1] << 8 | (uint32_t)seed[4 * i + 2] << 16 |
+             (uint32_t)seed[4 * i + 3] << 24;
+  uint64_t have = ~(uint64_t)0;  // the block in blk (no i / 4 is all ones)
+  for (size_t t = 0; t < count; t++) {
+    const uint64_t i = first + t;
+    if (i / 4 != have) {
+      have = i / 4;
+      chacha20_block_host(key, have, blk);
+    }
+    const uint32_t *w = blk + 4 * (i % 4);
+    uint64_t *o = out + 4 * t;
+    o[0] = (uint64_t)w[0] | (uint64_t)w[1] << 32;
+    o[1] = (uint64_t)w[2] | (uint64_t)w[3] << 32;
+    o[2] = o[3] = 0;
+    if (!(o[0] | o[1])) o[0] = 1;
+  }
 }
 
 // SumCheck::verify with claimed sum 0 (src/sumcheck.rs:113-150); round polynomials are

@@ -570,6 +570,50 @@ def _nonempty(a: np.ndarray) -> np.ndarray:
     return a if len(a) else np.zeros((1, 4), dtype=np.uint64)
 
 
+def _affine_limbs(pts: Sequence[G1Affine]) -> np.ndarray:
+    """[None | (x, y)] -> (n, 8) affine Montgomery limbs, identity = zeros (Srs.download()'s form)."""
+    out = np.zeros((len(pts), 8), dtype=np.uint64)
+    live = [i for i, p in enumerate(pts) if p is not None]
+    if live:
+        out[live, :4] = to_mont([pts[i][0] for i in live], P_MOD)
+        out[live, 4:] = to_mont([pts[i][1] for i in live], P_MOD)
+    return out
+
+
+def _proof_limbs(proofs) -> np.ndarray:
+    """An (n, 8) array as open_all returns it, or a list of KZGProof -> the (n, 8) array."""
+    if isinstance(proofs, np.ndarray):
+        return np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8)
+    return _affine_limbs([p.proof for p in proofs])
+
+
+def _seed_arg(seed: Optional[bytes]):
+    if seed is None:
+        return None
+    if len(seed) != 32:
+        raise InvalidParameters("seed must be 32 bytes")
+    return (C.c_uint8 * 32)(*seed)
+
+
+def _verify_many_call(call, locate: bool):
+    """Run call(ok, bad_index) of one of the batched verifiers: bool, or (bool, lowest failing index)."""
+    ok = C.c_int(0)
+    bad = C.c_uint64(0)
+    _check(call(C.byref(ok), C.pointer(bad) if locate else None))
+    if not locate:
+        return bool(ok.value)
+    return bool(ok.value), (None if ok.value else int(bad.value))
+
+
+def verify_challenges(seed: bytes, first: int, count: int) -> List[int]:
+    """The challenges [first, first + count) the batched verifiers draw from `seed` (tns_verify_challenges)."""
+    if seed is None:
+        raise InvalidParameters("verify_challenges needs the 32-byte seed")
+    out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+    N.load().tns_verify_challenges(_seed_arg(seed), first, count, N.p64(out))
+    return [_limbs_to_int(r) for r in out[:count]]
+
+
 class KZGCommitment:
     """``impl CommitmentScheme for KZGCommitment`` (src/commitments.rs:156-302), prover half."""
 
@@ -616,6 +660,26 @@ class KZGCommitment:
         _check(N.load().tns_kzg_batch_verify(C.byref(vk.raw), n, N.p64(cs), N.p64(to_mont(list(points))),
                                              N.p64(to_mont(list(values))), N.p64(ps), C.byref(ok)))
         return bool(ok.value)
+
+    @staticmethod
+    def verify_many(vk: "CommitmentVerificationKey", commitments, points, values, proofs,
+                    seed: Optional[bytes] = None, locate: bool = False, device: int = 0):
+        """k openings in one sound check on the device (tns_kzg_verify_many): `commitments` has k
+        entries or 1 (shared by all), `proofs` is a list of KZGProof or a (k, 8) array.  Unlike
+        batch_verify the equation holds for honest batches at distinct points, and with seed=None the
+        challenges come from the OS; a fixed public seed checks nothing against an adversary.
+        Returns bool, or with locate=True (bool, lowest failing index or None)."""
+        z, v, pis = _as_mont(points), _as_mont(values), _proof_limbs(proofs)
+        k = len(pis)
+        if not (len(z) == len(v) == k):
+            raise CommitmentError("Batch verify input lengths must match")
+        cs = _affine_limbs([c.commitment for c in commitments])
+        pad8 = np.zeros((1, 8), dtype=np.uint64)
+        ctx = Context.get(device)
+        return _verify_many_call(
+            lambda ok, bad: N.load().tns_kzg_verify_many(
+                ctx.handle, C.byref(vk.raw), N.p64(cs if len(cs) else pad8), len(cs), N.p64(_nonempty(z)),
+                N.p64(_nonempty(v)), N.p64(pis if k else pad8), k, _seed_arg(seed), ok, bad), locate)
 
     @staticmethod
     def commit_evaluations(params: CommitmentParams, evaluations) -> KZGCommitmentValue:
@@ -684,6 +748,23 @@ class KZGVectorCommitment:
     def verify(vk: "CommitmentVerificationKey", commitment: KZGCommitmentValue, index: int, value: int,
                proof: KZGProof) -> bool:
         return KZGCommitment.verify(vk, commitment, index, value, proof)
+
+    @staticmethod
+    def verify_all(vk: "CommitmentVerificationKey", commitment: KZGCommitmentValue, vector, proofs,
+                   seed: Optional[bytes] = None, locate: bool = False, device: int = 0):
+        """verify(vk, commitment, i, vector[i], proofs[i]) for every i in one sound check on the device
+        (tns_vc_verify_all): `proofs` is the (n, 8) array open_all returns, or a list of KZGProof.
+        seed=None draws the challenges from the OS (see KZGCommitment.verify_many).  Returns bool, or
+        with locate=True (bool, lowest failing index or None)."""
+        y, pis = _as_mont(vector), _proof_limbs(proofs)
+        n = len(y)
+        if len(pis) != n:
+            raise CommitmentError("Batch verify input lengths must match")
+        ctx = Context.get(device)
+        return _verify_many_call(
+            lambda ok, bad: N.load().tns_vc_verify_all(
+                ctx.handle, C.byref(vk.raw), N.p64(_affine_to_proj(commitment.commitment)), N.p64(_nonempty(y)), n,
+                N.p64(pis if n else np.zeros((1, 8), dtype=np.uint64)), _seed_arg(seed), ok, bad), locate)
 
 
 def msm(params: CommitmentParams, scalars) -> G1Affine:
@@ -1321,6 +1402,16 @@ def vc_open_all_resident(params: CommitmentParams, vector: DeviceBuffer, n: int,
     _check(N.load().tns_vc_open_all_device(params.srs.ctx.handle, params.srs.handle, vector.ptr, n, proofs.ptr))
 
 
+def vc_verify_all_resident(vk: "CommitmentVerificationKey", commitment: KZGCommitmentValue, vector: DeviceBuffer,
+                           n: int, proofs: DeviceBuffer, seed: Optional[bytes] = None, locate: bool = False):
+    """KZGVectorCommitment.verify_all on a vector (n Fr, Montgomery) and proofs (n affine points, as
+    vc_open_all_resident leaves them) resident in HBM: tns_vc_verify_all_device."""
+    return _verify_many_call(
+        lambda ok, bad: N.load().tns_vc_verify_all_device(
+            vector.ctx.handle, C.byref(vk.raw), N.p64(_affine_to_proj(commitment.commitment)), vector.ptr, n,
+            proofs.ptr, _seed_arg(seed), ok, bad), locate)
+
+
 # ----------------------------------------------------------------------------- one proof across GPUs
 _AllgatherFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -1629,7 +1720,8 @@ def profile_only(ctx: Context, stage=None):
 
 
 PROFILE_STAGES = ["msm_digits", "msm_sort", "msm_accumulate", "msm_fixup", "msm_reduce", "ntt_stage", "ntt_lds",
-                  "ntt_pointwise", "interp_tile", "interp_elementwise", "sumcheck_round", "open_scan"]
+                  "ntt_pointwise", "interp_tile", "interp_elementwise", "sumcheck_round", "open_scan",
+                  "verify_points", "verify_scalars"]
 
 
 def profile_read_ex(ctx: Context, stage: str) -> dict:
@@ -1675,5 +1767,5 @@ __all__ = [
     "MemoryOp", "MemoryTrace", "Twist", "TwistProof", "LookupOp", "LookupTable", "Shout", "ShoutProof",
     "bench_trace", "to_mont", "from_mont", "fr_from_u64_array", "device_count", "Comm", "setup_params_shard",
     "shard_slice", "bench_trace_slice", "KZGVectorCommitment", "CommitmentVerificationKey", "pairing",
-    "g1_serialize", "g1_deserialize",
+    "g1_serialize", "g1_deserialize", "verify_challenges",
 ]

@@ -159,6 +159,13 @@ SIGNATURES = [
     ("tns_verifier_key", C.c_int, [C.POINTER(TnsParams), C.POINTER(TnsVk)]),
     ("tns_kzg_verify", C.c_int, [C.POINTER(TnsVk), U64P, U64P, U64P, U64P, C.POINTER(C.c_int)]),
     ("tns_kzg_batch_verify", C.c_int, [C.POINTER(TnsVk), C.c_size_t, U64P, U64P, U64P, U64P, C.POINTER(C.c_int)]),
+    ("tns_kzg_verify_many", C.c_int,
+     [C.c_void_p, C.POINTER(TnsVk), U64P, C.c_size_t, U64P, U64P, U64P, C.c_size_t, U8P, C.POINTER(C.c_int), U64P]),
+    ("tns_vc_verify_all", C.c_int,
+     [C.c_void_p, C.POINTER(TnsVk), U64P, U64P, C.c_size_t, U64P, U8P, C.POINTER(C.c_int), U64P]),
+    ("tns_vc_verify_all_device", C.c_int,
+     [C.c_void_p, C.POINTER(TnsVk), U64P, C.c_void_p, C.c_size_t, C.c_void_p, U8P, C.POINTER(C.c_int), U64P]),
+    ("tns_verify_challenges", None, [U8P, C.c_uint64, C.c_size_t, U64P]),
     ("tns_twist_verify", C.c_int, [C.POINTER(TnsVk), C.POINTER(TnsProof), C.POINTER(C.c_int)]),
     ("tns_shout_verify", C.c_int, [C.POINTER(TnsVk), C.POINTER(TnsProof), C.POINTER(C.c_int)]),
     ("tns_pairing", C.c_int, [U64P, U64P, U64P]),
