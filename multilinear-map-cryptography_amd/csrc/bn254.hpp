@@ -186,6 +186,21 @@ TNS_HD Fp<C> dbl(const Fp<C> &a) {
 #else
 #include "mont_mul.inc"
 #endif
+#ifndef TNS_HAVE_MUL_X2  // a product variant without the interleaved pairs: one product after the other
+template <class C>
+__device__ __forceinline__ void mul_lazy_x2_dev(const Fp<C> &a0, const Fp<C> &b0, const Fp<C> &a1, const Fp<C> &b1,
+                                                Fp<C> &o0, Fp<C> &o1) {
+  const Fp<C> t = mul_lazy_dev(a0, b0);
+  o1 = mul_lazy_dev(a1, b1);
+  o0 = t;
+}
+template <class C>
+__device__ __forceinline__ void sqr_lazy_x2_dev(const Fp<C> &a0, const Fp<C> &a1, Fp<C> &o0, Fp<C> &o1) {
+  const Fp<C> t = sqr_lazy_dev(a0);
+  o1 = sqr_lazy_dev(a1);
+  o0 = t;
+}
+#endif
 #endif
 
 // Host (and reference): CIOS Montgomery product, no-carry variant (top modulus limb < 2^31 - 1).
@@ -740,23 +755,22 @@ __device__ __forceinline__ G1Xyzz xyzz_madd_lazy(const G1Xyzz &p, const G1Affine
     r.zzz = Fq::one();
     return r;
   }
-  const Fq U2 = mul_lazy_dev(q.x, p.zz);
-  const Fq S2 = mul_lazy_dev(q.y, p.zzz);
+  // the ten products go out as independent pairs (mul_lazy_x2_dev: the two products' asm
+  // statements alternate, so hipcc owes no wait state between them), Y3's pair product alone
+  Fq U2, S2;
+  mul_lazy_x2_dev(q.x, p.zz, q.y, p.zzz, U2, S2);
   const Fq P = sub2_dev(U2, p.x);
   const Fq R = sub2_dev(S2, p.y);
   if (fq_zero_lazy(P)) {
     if (fq_zero_lazy(R)) return xyzz_mdbl(q);
     return G1Xyzz::inf();
   }
-  // ordered for register pressure: ZZ1, ZZZ1 die in ZZ3 / ZZZ3 right after PP / PPP, X1 and PP
-  // in Q; the peak live set is PP, PPP, R, X1, Y1 and the two Z coordinates
-  const Fq PP = sqr_lazy_dev(P);
-  const Fq PPP = mul_lazy_dev(P, PP);
+  Fq PP, RR, PPP, Q;
+  sqr_lazy_x2_dev(P, R, PP, RR);
+  mul_lazy_x2_dev(P, PP, p.x, PP, PPP, Q);
   G1Xyzz r;
-  r.zz = mul_lazy_dev(p.zz, PP);
-  r.zzz = mul_lazy_dev(p.zzz, PPP);
-  const Fq Q = mul_lazy_dev(p.x, PP);
-  r.x = sub2_dev(sub2_dev(sqr_lazy_dev(R), PPP), add2_dev(Q, Q));
+  mul_lazy_x2_dev(p.zz, PP, p.zzz, PPP, r.zz, r.zzz);
+  r.x = sub2_dev(sub2_dev(RR, PPP), add2_dev(Q, Q));
   // Y3 = R (Q - X3) - Y1 PPP as ONE reduction of R (Q - X3) + Y1 (2M - PPP)  (PPP in [0, 2M))
   r.y = mul2_lazy_dev(R, sub2_dev(Q, r.x), p.y, const_minus_dev<FqCfg, true>(PPP));
   return r;

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Generate product-scanning Montgomery multiplications whose MACs are emitted G per inline-asm
 block (tools/mac_blocks.inc).  One asm block per MAC lets the compiler insert a wait state
-(s_nop) between consecutive blocks; larger blocks keep the carry chain inside one statement."""
+(s_nop) between consecutive blocks; larger blocks keep the carry chain inside one statement.
+Also writes the library's csrc/mont_mul.inc (whole columns per block; its header comment,
+LIB_HEADER, describes the column shift) and csrc/field_asm.inc.  Run from the repository root."""
 import sys
 
 
@@ -41,61 +43,107 @@ def one_products(k):
     return [(f"a.v[{k}]", "1u", "s")] if k < 8 else []
 
 
-def gen(G, name, reduce=True, square=False, pair=False, redc=False):
-    """reduce: True -> conditional subtraction of M; False -> none (lazy, inputs < 2M give < 2M);
-    "2m" -> subtraction of 2M (pair: Mont(a b + c d) < 2.51 M for inputs < 2M, back below 2M).
-    No asm statement has an early-clobber output (see emit)."""
+def gen_body(G, square=False, pair=False, redc=False):
+    """The declarations and the statements (one list entry each) of one product on the operands
+    a, b[, c, d]; the result is left in r[0..7].  No asm statement has an early-clobber output
+    (see emit)."""
     out = []
     products = sqr_products if square else ab_products
     if redc:  # a * 1: Montgomery reduction of a alone (the canonical value of a Montgomery form)
         products = one_products
-        args = "const Fp<C> &a"
     elif pair:
         products = lambda k: ab_products(k) + cd_products(k)
-        args = "const Fp<C> &a, const Fp<C> &b, const Fp<C> &c, const Fp<C> &d"
-    elif not redc:
-        args = "const Fp<C> &a" if square else "const Fp<C> &a, const Fp<C> &b"
-    out.append(f"template <class C>\n__device__ __forceinline__ Fp<C> {name}({args}) {{")
-    if square:
-        out.append(SQR_PRELUDE)
-    out.append("  u32 m[8], r[8];\n  unsigned long long acc = 0;\n  u32 c2 = 0;")
+    decls = ([SQR_PRELUDE] if square else []) + ["  u32 m[8], r[8];\n  unsigned long long acc;\n  u32 c2;"]
 
-    def emit(macs):
-        # macs: list of (xexpr, yexpr, ycons).  acc and the carry word c2 are both TIED operands
-        # ("+v"), c2 zeroed before the column: no early-clobber output.  hipcc (ROCm 7.2) allocated
-        # an early-clobber carry word on the register of a live input (a.v[7]) when it coalesced
-        # the word into the next column's 64-bit pair (tools/chainfuse.hip, DESIGN.md 2.6)
+    MAD = "v_mad_u64_u32 %0, vcc, %{x}, %{y}, %0"
+
+    def stmt(body, outs, macs):
+        ins = []
+        for x, y, yc in macs:
+            ins += [f'"v"({x})', f'"{yc}"({y})']
+        out.append('  asm("' + "\\n\\t".join(body) + '" : ' + outs + " : " + ", ".join(ins) + ' : "vcc");')
+
+    def emit(macs, opens=True, carries=True):
+        # macs: list of (xexpr, yexpr, ycons), one column's (or its Montgomery step's) multiply-adds.
+        # opens: the first MAC creates the column's overflow word c2 from constants (0 + 0 + carry)
+        # instead of adding into a word zeroed beforehand.  c2 is then a fresh, untied output, legal
+        # WITHOUT an early clobber only as the destination of its statement's last instruction (every
+        # input has been read by then), so that MAC and its carry are a statement of their own.
+        # Everywhere else acc and c2 are TIED operands ("+v"): no statement has an early-clobber
+        # output.  hipcc (ROCm 7.2) allocated an early-clobber carry word on the register of a live
+        # input (a.v[7]) when it coalesced the word into the next column's 64-bit pair
+        # (tools/chainfuse.hip, DESIGN.md 2.6)
+        # carries=False: no MAC of the list can carry out of the 64-bit accumulator (the caller
+        # states the bound); VCC is still written, nothing reads it.
+        if not carries:
+            for s in range(0, len(macs), G):
+                grp = macs[s:s + G]
+                stmt([MAD.format(x=1 + 2 * t, y=2 + 2 * t) for t in range(len(grp))], '"+v"(acc)', grp)
+            return
+        if opens:
+            stmt([MAD.format(x=2, y=3), "v_addc_co_u32_e64 %1, vcc, 0, 0, vcc"], '"+v"(acc), "=v"(c2)', macs[:1])
+            macs = macs[1:]
         for s in range(0, len(macs), G):
             grp = macs[s:s + G]
             body = []
-            ins = []
-            for t, (x, y, yc) in enumerate(grp):
-                xi, yi = 2 + 2 * t, 3 + 2 * t
-                body.append(f"v_mad_u64_u32 %0, vcc, %{xi}, %{yi}, %0")
+            for t in range(len(grp)):
+                body.append(MAD.format(x=2 + 2 * t, y=3 + 2 * t))
                 body.append("v_addc_co_u32_e32 %1, vcc, 0, %1, vcc")
-                ins.append(f'"v"({x})')
-                ins.append(f'"{yc}"({y})')
-            out.append('  asm("' + "\\n\\t".join(body) + '" : "+v"(acc), "+v"(c2) : ' + ", ".join(ins) +
-                       ' : "vcc");')
+            stmt(body, '"+v"(acc), "+v"(c2)', grp)
 
+    # Column shift: the sum moves down one word, acc = acc >> 32 | c2 << 32.  c2 is a new value in
+    # every column, so the register allocator homes it in the odd half of the pair the NEXT column
+    # accumulates into, and the shift is the one move "next pair's low word = this pair's high
+    # word"; two pairs alternate.  (Recycling the low word a Montgomery step cleared as the next
+    # zero carry word, as before, put that zero in an even register: every second shift then took
+    # two moves, and columns 8-14 a copy of a zero register each.)
+    SHIFT = "  acc = (acc >> 32) | ((unsigned long long)c2 << 32);"
+    # Dead carries, by the size of T = (the products) + m M, m < 2^256:
+    #   canonical (mul_ps_dev, redc_dev):  T < M^2 + M 2^256
+    #   lazy (mul_lazy_dev, sqr_lazy_dev), inputs <= 2M (the closed domain of mle.hip included):
+    #                                      T <= 4M^2 + M 2^256
+    #   pair (mul2_lazy_dev), inputs <= 2M: T <= 8M^2 + M 2^256
+    # With M < 2^254 all of them are below 2^509 + 2^510 < 2^512.  The column sums add T up from
+    # its low end, every partial sum is <= T, and entering column k the accumulator holds the
+    # partial sum >> 32 k.  So in column 14 the accumulator never exceeds T >> 448 < 2^64: none of
+    # its MACs carries, and r[7] is its high word.  Column 0's first MAC adds one 64-bit product to
+    # nothing: it is written as the product alone (src2 = 0), which also spares zeroing acc.
     for k in range(8):
         macs = products(k)
         macs += [(f"m[{i}]", f"C::M[{k - i}]", "s") for i in range(k)]
-        emit(macs)
+        if k == 0:
+            x, y, yc = macs[0]
+            out.append(f"  acc = (unsigned long long){x} * {y};")
+            macs = macs[1:]
+        if macs:
+            emit(macs)
         out.append(f"  m[{k}] = (u32)acc * C::INV;")
-        emit([(f"m[{k}]", "C::M[0]", "s")])  # its own block: m[k] depends on the column sum
-        # the reduction cleared the low word: it is the next column's zero carry word (no move)
-        out.append("  {\n    const u32 z = (u32)acc;\n    acc = (acc >> 32) | ((unsigned long long)c2 << 32);\n"
-                   "    c2 = z;\n  }")
+        # its own block: m[k] depends on the column sum
+        emit([(f"m[{k}]", "C::M[0]", "s")], opens=not macs)
+        out.append(SHIFT)
     for k in range(8, 15):
         macs = products(k)
         macs += [(f"m[{i}]", f"C::M[{k - i}]", "s") for i in range(k - 7, 8)]
-        emit(macs)
+        emit(macs, carries=k < 14)
         out.append(f"  r[{k - 8}] = (u32)acc;")
-        out.append("  acc = (acc >> 32) | ((unsigned long long)c2 << 32);")
         if k < 14:
-            out.append("  c2 = 0;")
-    out.append("  r[7] = (u32)acc;\n  Fp<C> o;\n#pragma unroll\n  for (int i = 0; i < 8; i++) o.v[i] = r[i];")
+            out.append(SHIFT)
+        else:
+            out.append("  acc >>= 32;")
+    out.append("  r[7] = (u32)acc;")
+    return decls, out
+
+
+def gen(G, name, reduce=True, square=False, pair=False, redc=False):
+    """reduce: True -> conditional subtraction of M; False -> none (lazy, inputs < 2M give < 2M);
+    "2m" -> subtraction of 2M (pair: Mont(a b + c d) < 2.51 M for inputs < 2M, back below 2M)."""
+    if pair:
+        args = "const Fp<C> &a, const Fp<C> &b, const Fp<C> &c, const Fp<C> &d"
+    else:
+        args = "const Fp<C> &a" if square or redc else "const Fp<C> &a, const Fp<C> &b"
+    decls, steps = gen_body(G, square, pair, redc)
+    out = [f"template <class C>\n__device__ __forceinline__ Fp<C> {name}({args}) {{"] + decls + steps
+    out.append("  Fp<C> o;\n#pragma unroll\n  for (int i = 0; i < 8; i++) o.v[i] = r[i];")
     if reduce == "2m":
         out.append("  reduce_once_2m_dev(o);\n  return o;\n}\n")
     else:
@@ -103,14 +151,100 @@ def gen(G, name, reduce=True, square=False, pair=False, redc=False):
     return "\n".join(out)
 
 
+def step_kind(text):
+    """asm: an inline-asm statement; free: a word of the accumulator taken as a result limb (no
+    instruction); valu: C the compiler turns into one VALU instruction (column 0's product, m[k],
+    the column shift's move)."""
+    if text.startswith("  asm("):
+        return "asm"
+    return "free" if text.startswith("  r[") or text.startswith("  acc >>=") else "valu"
+
+
+def interleave(steps0, steps1, window=6):
+    """Merge two independent products' statement lists into the order that costs the fewest wait
+    states.  hipcc (gfx950) puts an s_nop after an asm statement when the next instruction is
+    another asm statement (any: they all write VCC) or reads the statement's outputs -- within
+    one product that is the next step, whatever it is.  Each list stays in order and the two stay
+    within `window` steps of each other (register pressure).  Dynamic programming over (steps
+    taken of each, what the last instruction was); returns [(which product, step index)]."""
+    kinds = [[step_kind(t) for t in steps0], [step_kind(t) for t in steps1]]
+    n = [len(steps0), len(steps1)]
+    best = {(0, 0, "valu", 0): (0, None)}  # state -> (wait states so far, previous state)
+    order = sorted((i + j, i, j) for i in range(n[0] + 1) for j in range(n[1] + 1) if abs(i - j) <= window)
+    for _, i, j in order:
+        for last in ("valu", "asm"):
+            for who in (0, 1):
+                st = (i, j, last, who)
+                if st not in best:
+                    continue
+                cost = best[st][0]
+                for c in ((0, 1) if i <= j else (1, 0)):  # ties go to the product that is behind
+                    pos = (i, j)[c]
+                    if pos == n[c] or abs(i + (c == 0) - j - (c == 1)) > window:
+                        continue
+                    k = kinds[c][pos]
+                    if k == "free":
+                        nxt, add = (i + (c == 0), j + (c == 1), last, who), 0
+                    else:
+                        add = int(last == "asm" and (k == "asm" or who == c))
+                        nxt = (i + (c == 0), j + (c == 1), k, c)
+                    if nxt not in best or best[nxt][0] > cost + add:
+                        best[nxt] = (cost + add, (st, c, pos))
+    end = min((v[0], k) for k, v in best.items() if k[0] == n[0] and k[1] == n[1])[1]
+    seq = []
+    while best[end][1] is not None:
+        prev, c, pos = best[end][1]
+        seq.append((c, pos))
+        end = prev
+    return seq[::-1]
+
+
+def gen_x2(G, name, square=False):
+    """Two independent lazy products (or squares) in one instruction stream: (a0 b0, a1 b1) ->
+    (o0, o1).  Inside one product every statement continues the one before, so hipcc owes a wait
+    state at every boundary; with a second, independent product at hand most boundaries can be
+    followed by an instruction of the other product (interleave).  The order is pinned with
+    scheduling barriers -- left alone, the machine scheduler regroups the statements.  The
+    results are written after the last statement, so an output may be one of the inputs."""
+    import re
+    both = []
+    for sfx in "01":
+        decls, steps = gen_body(G, square)
+        ren = lambda t: re.sub(r"\b(acc|c2|m|r|d|e|a|b)\b", lambda mo: mo.group(1) + sfx, t)
+        both.append(([ren(t) for t in decls], [ren(t) for t in steps]))
+    args = ("const Fp<C> &x0, const Fp<C> &x1" if square else
+            "const Fp<C> &x0, const Fp<C> &y0, const Fp<C> &x1, const Fp<C> &y1")
+    out = [f"template <class C>\n__device__ __forceinline__ void {name}({args}, Fp<C> &o0, Fp<C> &o1) {{"]
+    # operands that still sit in memory are loaded here, ahead of the first barrier: a load left at
+    # its first use could not be moved up any more and would be waited for inside the product
+    out.append("  const Fp<C> a0 = x0, a1 = x1;" if square else "  const Fp<C> a0 = x0, b0 = y0, a1 = x1, b1 = y1;")
+    out += both[0][0] + both[1][0]
+    for c, pos in interleave(both[0][1], both[1][1]):
+        text = both[c][1][pos]
+        out.append(text if step_kind(text) == "free" else text + "\n  __builtin_amdgcn_sched_barrier(0);")
+    out.append("#pragma unroll\n  for (int i = 0; i < 8; i++) o0.v[i] = r0[i], o1.v[i] = r1[i];\n}\n")
+    return "\n".join(out)
+
+
 LIB_HEADER = """// mont_mul.inc -- generated by tools/gen_mac_blocks.py (do not edit): the device Montgomery
 // product of bn254.hpp.  Product scanning: column k accumulates every a_i b_j and m_i M_j with
 // i + j = k into a 64-bit register pair with v_mad_u64_u32, whose carry-out (VCC) feeds a
-// 32-bit overflow word via v_addc_co_u32 (both tied asm operands: no early-clobber outputs, see
-// tools/gen_mac_blocks.py gen/emit).  Each column's MACs (up to 16) go out as one
+// 32-bit overflow word via v_addc_co_u32.  Each column's MACs (up to 16) go out as one
 // inline-asm block: the compiler separates consecutive asm statements by a wait state (s_nop),
 // so one MAC per statement cost ~1 nop per MAC (tools/mulbench2.hip: Fq mul 112 -> 117 G/s with
 // blocks of 8; tools/maddbench.hip: XYZZ madd 10.51 -> 10.66 G/s from 8 to whole columns).
+// The column shift: a column's overflow word is a NEW value, created by the column's first carry
+// instruction from constants (v_addc_co_u32_e64 c2, vcc, 0, 0, vcc), so the register allocator
+// homes it in the odd half of the pair the next column accumulates into and the shift is one
+// move (next pair's low word = this pair's high word); two pairs alternate, nothing is zeroed
+// or copied beforehand.  That first MAC and its carry are a two-instruction statement of their
+// own: the fresh word is the destination of the statement's LAST instruction, the one place
+// where an untied output needs no early clobber; everywhere else the accumulator and the word
+// are tied operands -- no statement has an early-clobber output (tools/gen_mac_blocks.py emit).
+// Carries that cannot occur have no instruction: column 0's first MAC is the product alone, and
+// column 14 cannot overflow 64 bits because the whole sum is below 2^512 (bounds: gen_body).
+// mul_lazy_x2_dev / sqr_lazy_x2_dev run two independent products in one instruction stream, in
+// the order that owes the fewest wait states (gen_x2 / interleave).
 """
 
 G_LIB = int(__import__("os").environ.get("TNS_MAC_BLOCK", "16"))
@@ -123,6 +257,7 @@ if __name__ == "__main__":
             f.write(gen(G, f"mul_blk{G}") + "\n")
     with open("multilinear-map-cryptography_amd/csrc/mont_mul.inc", "w") as f:
         f.write(LIB_HEADER)
+        f.write("#define TNS_HAVE_MUL_X2 1  // mul_lazy_x2_dev / sqr_lazy_x2_dev are defined here\n")
         f.write("// a b / R mod M, canonical: a, b in [0, M) -> [0, M) (any a b < M 2^256 would do: the sum is\n"
                 "// below 2M before the one conditional subtraction)\n")
         f.write(gen(G_LIB, "mul_ps_dev") + "\n")
@@ -133,6 +268,10 @@ if __name__ == "__main__":
         f.write("// the lazy product a * a: 36 products instead of 64 (input <= 2M < 2^255, see sqr_products;\n"
                 "// result < 2M as mul_lazy_dev's)\n")
         f.write(gen(G_LIB, "sqr_lazy_dev", reduce=False, square=True) + "\n")
+        f.write("// two independent lazy products / squares at once, statement by statement (see gen_x2): the\n"
+                "// mixed addition's products come in independent pairs (bn254.hpp xyzz_madd_lazy)\n")
+        f.write(gen_x2(G_LIB, "mul_lazy_x2_dev") + "\n")
+        f.write(gen_x2(G_LIB, "sqr_lazy_x2_dev", square=True) + "\n")
         f.write("// Mont(a b + c d) with ONE reduction for inputs < 2M: the column sums take both products\n"
                 "// (T < 8M^2 < 1.52 M 2^256, so the result is < 2.51 M) and a subtraction of 2M brings it back\n"
                 "// below 2M -- 64 multiply-adds fewer than two products and an addition\n")

@@ -1,6 +1,7 @@
 // maddbench.hip -- library Fq product and XYZZ mixed addition (the MSM accumulation step)
 // throughput on gfx950 for one build variant of the device arithmetic:
-//   -DTNS_MONT_MUL_INC='"<file>"'  product variant (default: csrc/mont_mul.inc)
+//   -DTNS_MONT_MUL_INC='"<file>"'  product variant (default: csrc/mont_mul.inc); a variant without
+//                                   the paired products (no TNS_HAVE_MUL_X2) runs them one after the other
 //   -DTNS_NO_FIELD_ASM             C add/sub/conditional subtraction instead of field_asm.inc
 // Built here and run on the GPU box by tools/maddbench.sh; prints one line.
 #include <hip/hip_runtime.h>
