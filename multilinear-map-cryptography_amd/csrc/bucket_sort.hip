@@ -30,19 +30,9 @@
 
 namespace tns {
 
-#ifndef TNS_BS_BLOCK
-#define TNS_BS_BLOCK 256
-#endif
-constexpr int BS_BLOCK = TNS_BS_BLOCK;  // 4 waves: fits the slots k_accumulate leaves free
-constexpr int BS_MAXBITS = 9;  // key bits per pass
-constexpr int BS_MAXBINS = 1 << BS_MAXBITS;
-#ifndef TNS_BS_TILE_MAX
-#define TNS_BS_TILE_MAX 8192
-#endif
-constexpr int BS_TILE = TNS_BS_TILE_MAX;  // entries per tile at most (LDS staging: 8 B each, 64 KiB at 8192)
-// per-pass tile sizes (template parameter TILE of the scatter kernels): 8192 or 4096 entries
+// (BS_BLOCK, BS_MAXBITS, BS_MAXBINS, BS_TILE, SCAN_SMALL, KF_*: msm_plan.hpp, with the geometry;
+// template parameter TILE of the scatter kernels: 8192 or 4096 entries)
 constexpr int BS_SCALARS = 4;  // scalars a pass-1 thread loads ahead
-
 
 struct DigitArgs {
   const Fr *scalars;
@@ -169,14 +159,12 @@ __device__ __forceinline__ void block_scan_bins(const uint32_t *h, uint32_t *out
 
 static_assert(BS_MAXBINS <= 2 * BS_BLOCK, "two bins per thread in the block scan");
 
-// Key formats between passes (BucketSortJob::kf): the keys a pass writes only need the key bits
+// Key formats between passes (SortGeom::kf): the keys a pass writes only need the key bits
 // the later passes still sort by.  KF_U32: 4-byte keys; KF_U16: 2-byte keys (<= 16 bits left: the
 // keys into the last pass, whose <= 9 key bits are all it reads).  (2-byte keys out of pass 1 too,
 // the 17th bit carried in the value, measured slower: pass 1 +0.2 ms, pass 2 +0.35 ms per 2^24
 // opening, their ~64-byte runs of half-dword stores costing more than the bytes saved.)
-enum { KF_U32 = 0, KF_U16 = 1 };
-
-// the scatters' stores (plain: non-temporal stores measured +1.3-2.1 ms per C4 step,
+// The scatters' stores (plain: non-temporal stores measured +1.3-2.1 ms per C4 step,
 // profiles/r06_ab_sort_nt.txt)
 template <class T>
 __device__ __forceinline__ void st_out(T *p, T v) {
@@ -376,19 +364,18 @@ __global__ void __launch_bounds__(BS_BLOCK) k_bs_scatter1_ct(DigitArgs A, int sh
   write_tile(lk, lv, m, lbase, goff, [&](uint32_t key) { return key >> shift; }, kf, keys, vals);
 }
 
-// compile-time plans of the pass-1 kernels: the fixed-base table windows (n = 2^20..2^26) and
-// the narrow trace commitments' per-window plans; anything else takes the runtime kernels
-struct Pass1Plan {
-  int tile, c, W;
+// the compile-time pass-1 kernels, in the order of msm_plan.hpp's kPass1Shapes (SortGeom::ct
+// indexes both tables)
+struct Pass1Kernels {
   void (*count)(DigitArgs, int, int, size_t, uint32_t *, unsigned *, uint64_t *);
   void (*scatter)(DigitArgs, int, int, size_t, const uint32_t *, int, uint32_t *, uint32_t *);
-  int spt;
 };
-#define TNS_P1(T, C, W, SPT) {T, C, W, k_bs_count1_ct<C, W>, k_bs_scatter1_ct<T, C, W, SPT>, SPT}
-static const Pass1Plan kPass1Plans[] = {
-    TNS_P1(BS_TILE, 22, 12, 3), TNS_P1(BS_TILE, 20, 13, 3), TNS_P1(BS_TILE, 19, 14, 3),
-    TNS_P1(BS_TILE, 17, 15, 3), TNS_P1(BS_TILE, 16, 2, 16), TNS_P1(BS_TILE, 12, 2, 16)};
+#define TNS_P1(K)                                                 \
+  {k_bs_count1_ct<kPass1Shapes[K].c, kPass1Shapes[K].W>, \
+   k_bs_scatter1_ct<BS_TILE, kPass1Shapes[K].c, kPass1Shapes[K].W, kPass1Shapes[K].spt>}
+static const Pass1Kernels kPass1Kernels[] = {TNS_P1(0), TNS_P1(1), TNS_P1(2), TNS_P1(3), TNS_P1(4), TNS_P1(5)};
 #undef TNS_P1
+static_assert(sizeof(kPass1Kernels) / sizeof(kPass1Kernels[0]) == kPass1ShapeCount, "one kernel pair per pass-1 shape");
 
 // bins of pass 1 -> segment starts; seg[nbins] = total = number of entries (also *valid)
 __global__ void k_bs_segs1(const uint32_t *__restrict__ offs, int nbins, size_t T1, uint32_t *__restrict__ seg,
@@ -735,10 +722,6 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_apply(const uint32_t *__r
 // microseconds each were most of the cost).  2^15: the last pass of a 2^24-scalar opening MSM has
 // 65 537 segments, whose one-block geometry took ~0.3 ms beside the other lane's scatter (16 serial
 // rounds); the multi-block tiles + scans take ~0.1 ms (C4 -0.17 ms, profiles/r06_ab_sort_geom_threshold.txt)
-#ifndef TNS_SCAN_SMALL_LOG  // (build-time A/B only)
-#define TNS_SCAN_SMALL_LOG 15
-#endif
-constexpr size_t SCAN_SMALL = (size_t)1 << TNS_SCAN_SMALL_LOG;
 __global__ void __launch_bounds__(ONE_BLOCK) k_scan_single(const uint32_t *__restrict__ in, size_t n,
                                                       uint32_t *__restrict__ out) {
   __shared__ uint32_t lds[ONE_BLOCK / 64];
@@ -832,37 +815,6 @@ static void exclusive_scan(hipStream_t st, DevBuf &tmp, const uint32_t *in, uint
   TNS_LAUNCH_CHECK();
 }
 
-// Pass 1's geometry for W*n entries of `bucket_bits`-bit buckets: key bits and passes, the
-// compile-time plan (if any), scalars per tile, tiles, bins, shift and the count buffer's length
-struct Pass1Geom {
-  int keybits = 0, npass = 0, wb = 0, bits0 = 0, nb = 0, shift = 0;
-  const Pass1Plan *ct = nullptr;
-  size_t spb = 0, T1 = 0, cnt_len = 0;
-};
-static Pass1Geom pass1_geom(size_t n, int c, int W, bool shared, int bucket_bits) {
-  Pass1Geom g;
-  if (shared)
-    while ((1 << g.wb) < W) g.wb++;
-  g.keybits = bucket_bits + g.wb;
-  g.npass = std::max(1, (g.keybits + BS_MAXBITS - 1) / BS_MAXBITS);
-  // the last pass sorts LDS-sized segments by BS_MAXBITS bits; the passes before it split the
-  // remaining bits evenly (25-bit keys: 8, 8, 9 -- pass 2 with 256 instead of 512 bins writes
-  // 128-byte runs: 1.21 -> 1.02 ms at 2^24)
-  const int last = std::min(g.keybits, BS_MAXBITS);
-  g.bits0 = g.npass == 1 ? last : (g.keybits - last + (g.npass - 2)) / (g.npass - 1);
-  g.nb = 1 << g.bits0;
-  g.shift = g.keybits - g.bits0;
-  for (const Pass1Plan &p : kPass1Plans)
-    if (p.tile == BS_TILE && p.c == c && p.W == W) g.ct = &p;
-  g.spb = (size_t)BS_TILE / W;
-  if (g.ct) g.spb = std::min(g.spb, (size_t)BS_BLOCK * g.ct->spt);
-  g.T1 = (n + g.spb - 1) / g.spb;
-  const size_t E = (size_t)W * n, max_seg = (size_t)1 << g.keybits, tmin = 4096;
-  const size_t max_tiles = (E + tmin - 1) / tmin + (max_seg >> last) + 1;
-  g.cnt_len = std::max((size_t)g.nb * g.T1, (size_t)BS_MAXBINS * max_tiles) + 1;
-  return g;
-}
-
 // Groups the W*n digit entries of `scalars` by bucket (bucket_bits bits of bucket index;
 // per-window layout: window bits included).  The result (BucketOrder): the key/value arrays
 // holding it (two of the lane's four entry buffers), the bucket starts (bucket b =
@@ -876,138 +828,75 @@ static Pass1Geom pass1_geom(size_t n, int c, int W, bool shared, int bucket_bits
 // instead of lane a's ~20 (0.35 ms of launch overhead on the critical lane), and each lane's
 // last pass starts as soon as ITS readback lands (a single host wait would hold lane a's last
 // pass behind lane b's first two passes: ~1.7 ms of an idle lane per 2^24 opening pair).
-void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, int c, int W, bool shared, uint32_t stride,
-                       int bucket_bits, uint32_t *valid, BucketSortJob &J) {
+void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, const WindowPlan &plan, uint32_t *valid,
+                       BucketSortJob &J) {
   hipStream_t st = ln.stream;
-  const size_t E = (size_t)W * n;
-  if (E >= ((size_t)1 << 32)) throw Error(TNS_ERR_COMMITMENT, "MSM too large for one bucket sort");
-  if (W > BS_TILE) throw Error(TNS_ERR_COMMITMENT, "too many MSM windows");
+  if ((size_t)plan.W * n >= ((size_t)1 << 32)) throw Error(TNS_ERR_COMMITMENT, "MSM too large for one bucket sort");
+  if (plan.W > BS_TILE) throw Error(TNS_ERR_COMMITMENT, "too many MSM windows");
   J = BucketSortJob();
   J.ln = &ln;
   J.valid = valid;
-  J.E = E;
-  J.bucket_bits = bucket_bits;
-  uint32_t **K = J.K, **V = J.V;
-  K[0] = (uint32_t *)ln.sort.keys[0].ensure(sizeof(uint32_t) * E);
-  K[1] = (uint32_t *)ln.sort.keys[1].ensure(sizeof(uint32_t) * E);
-  V[0] = (uint32_t *)ln.sort.vals[0].ensure(sizeof(uint32_t) * E);
-  V[1] = (uint32_t *)ln.sort.vals[1].ensure(sizeof(uint32_t) * E);
-  DigitArgs A{in.fr, n, 0, c, W, 0, shared, stride, in.mont, in.u64, in.n_u64};
-  if (shared)
-    while ((1 << A.wb) < W) A.wb++;
-  J.wb = A.wb;
-  const int keybits = bucket_bits + A.wb;
-  const int npass = std::max(1, (keybits + BS_MAXBITS - 1) / BS_MAXBITS);
-  int *bits = J.bits;
-  // the last pass sorts LDS-sized segments by BS_MAXBITS bits; the passes before it split the
-  // remaining bits evenly (25-bit keys: 8, 8, 9 -- pass 2 with 256 instead of 512 bins writes
-  // 128-byte runs: 1.21 -> 1.02 ms at 2^24)
-  bits[npass - 1] = std::min(keybits, BS_MAXBITS);
-  // packed tail: the second-to-last pass writes (last-pass key bits, sign, point index) as one
-  // word when they fit (n <= 2^22 with a 9-bit last pass).  (A 7-bit last pass for 2^24 points,
-  // 9, 9, 7, measured slower: it moved the cost into 512-bin passes, +3.3 ms of sort per C4 step
-  // against -0.8 ms of reads.)  Values-only last pass (vo): whenever there is more than one pass --
-  // the accumulation reads no keys (C4: k_accumulate 9.10 -> 8.8 ms).
-  int ibits = 1;
-  while (((size_t)1 << ibits) < n) ibits++;
-  J.vo = npass >= 2;
-  // (unpack_value reads the window index from the low wb bits of the last pass's L key bits: L >= wb)
-  J.pk = J.vo && npass >= 3 && bits[npass - 1] + ibits + 1 <= 32 && bits[npass - 1] >= J.wb;
-  for (int p = 0, rest = keybits - bits[npass - 1]; p < npass - 1; p++) {
-    bits[p] = (rest + (npass - 2 - p)) / (npass - 1 - p);
-    rest -= bits[p];
-  }
-  J.ibits = ibits;
-  J.shared = shared;
-  J.stride = stride;
-  // key formats between passes: 2-byte keys into the last pass (its <= 9 key bits; C4 openings:
-  // pass 2 -> 3, sort kernels -0.6 ms per step, profiles/r03_ab_sort_k16.txt), 4-byte keys elsewhere
-  for (int p = 0, rest = keybits; p < npass - 1; p++) {
-    rest -= bits[p];
-    J.kf[p] = J.vo && p == npass - 2 && rest <= 16 ? KF_U16 : KF_U32;
-  }
-  if (J.pk) J.kf[npass - 2] = KF_U32;  // the packed words (pack_entry) are 4-byte
-  int shift = keybits - bits[0];
+  const SortGeom &g = J.g = sort_geom(n, plan);
+  uint32_t **K = J.K, **V = J.V, **seg = J.seg;
+  for (int k = 0; k < 2; k++) K[k] = (uint32_t *)ln.sort.keys[k].ensure(sizeof(uint32_t) * g.E);
+  for (int k = 0; k < 2; k++) V[k] = (uint32_t *)ln.sort.vals[k].ensure(sizeof(uint32_t) * g.E);
+  for (int k = 0; k < 2; k++) seg[k] = (uint32_t *)ln.sort.seg[k].ensure(sizeof(uint32_t) * (g.max_seg + 1));
+  const bool pre = in.precounted && g.ct >= 0 && same_counts(in.pre, plan) && ln.sort.counts.p == in.precounted &&
+                   ln.sort.counts.bytes >= sizeof(uint32_t) * g.cnt_len;
+  uint32_t *counts = J.counts = (uint32_t *)ln.sort.counts.ensure(sizeof(uint32_t) * g.cnt_len);
+  uint32_t *offs = J.offs = (uint32_t *)ln.sort.offs.ensure(sizeof(uint32_t) * g.cnt_len);
 
-  // pass 1: scalars -> bins of the top bits[0] key bits (a compile-time plan's kernels when there
-  // is one for this window plan, else the runtime-plan kernels)
-  const int tile1 = BS_TILE;
-  const Pass1Plan *ct = nullptr;
-  for (const Pass1Plan &p : kPass1Plans)
-    if (p.tile == tile1 && p.c == c && p.W == W) ct = &p;
-  if ((size_t)tile1 < (size_t)W) throw Error(TNS_ERR_INVALID_PARAMETERS, "bucket sort: more windows than a pass-1 tile holds");
-  A.spb = (size_t)tile1 / W;
-  if (ct) A.spb = std::min(A.spb, (size_t)BS_BLOCK * ct->spt);
-  const size_t T1 = (n + A.spb - 1) / A.spb;
-  int nb = 1 << bits[0];
-  const Pass1Geom pg = pass1_geom(n, c, W, shared, bucket_bits);
-  if (pg.bits0 != bits[0] || pg.T1 != T1 || pg.ct != ct || pg.shift != shift)
-    throw Error(TNS_ERR_DEVICE, "bucket sort: pass-1 geometry mismatch");
-  const size_t max_seg = (size_t)1 << keybits;
-  uint32_t **seg = J.seg;
-  seg[0] = (uint32_t *)ln.sort.seg[0].ensure(sizeof(uint32_t) * (max_seg + 1));
-  seg[1] = (uint32_t *)ln.sort.seg[1].ensure(sizeof(uint32_t) * (max_seg + 1));
-  const size_t tmin = 4096;  // the smallest pass tile
-  const size_t max_tiles = (E + tmin - 1) / tmin + (max_seg >> bits[npass - 1]) + 1;
-  const size_t cnt_len = std::max((size_t)nb * T1, (size_t)BS_MAXBINS * max_tiles) + 1;
-  const bool pre = in.precounted && ct && in.pre_shared == shared && in.pre_c == c && in.pre_W == W &&
-                   ln.sort.counts.p == in.precounted && ln.sort.counts.bytes >= sizeof(uint32_t) * cnt_len;
-  uint32_t *counts = J.counts = (uint32_t *)ln.sort.counts.ensure(sizeof(uint32_t) * cnt_len);
-  uint32_t *offs = J.offs = (uint32_t *)ln.sort.offs.ensure(sizeof(uint32_t) * cnt_len);
-  if (!pre) {  // (precounted: quotient2_count_dev wrote them)
-    if (ct) ct->count<<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, counts, nullptr, nullptr);
-    else k_bs_count1<<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, counts);
+  // pass 1: scalars -> bins of the top bits[0] key bits (the compile-time kernels when there are
+  // some for this window plan, else the runtime-plan kernels)
+  const DigitArgs A{in.fr, n, g.spb, plan.c, plan.W, g.wb, plan.shared, plan.stride, in.mont, in.u64, in.n_u64};
+  const Pass1Kernels *ct = g.ct >= 0 ? &kPass1Kernels[g.ct] : nullptr;
+  const unsigned T1 = (unsigned)g.T1;
+  if (!pre) {  // (precounted: quotient2_count_dev or bucket_sort_precount_bits wrote them)
+    if (ct) ct->count<<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, counts, nullptr, nullptr);
+    else k_bs_count1<<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, counts);
     TNS_LAUNCH_CHECK();
   }
-  exclusive_scan(st, ln.sort.scan, counts, offs, (size_t)nb * T1 + 1);
-  const int kf1 = npass > 1 ? J.kf[0] : KF_U32;
-  if (ct) ct->scatter<<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, offs, kf1, K[0], V[0]);
-  else k_bs_scatter1<BS_TILE><<<(unsigned)T1, BS_BLOCK, 0, st>>>(A, shift, nb, T1, offs, kf1, K[0], V[0]);
+  exclusive_scan(st, ln.sort.scan, counts, offs, (size_t)g.nb * g.T1 + 1);
+  const int kf1 = g.npass > 1 ? g.kf[0] : KF_U32;
+  if (ct) ct->scatter<<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, offs, kf1, K[0], V[0]);
+  else k_bs_scatter1<BS_TILE><<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, offs, kf1, K[0], V[0]);
   TNS_LAUNCH_CHECK();
-  k_bs_segs1<<<1, 256, 0, st>>>(offs, nb, T1, seg[0], valid);
+  k_bs_segs1<<<1, 256, 0, st>>>(offs, g.nb, g.T1, seg[0], valid);
   TNS_LAUNCH_CHECK();
 
-  J.S = nb;
-  J.cur = 0;
-  J.tcount = (uint32_t *)ln.sort.tiles.ensure(sizeof(uint32_t) * 2 * (max_seg + 1));
-  J.tbase = J.tcount + (max_seg + 1);
-  J.desc = (uint32_t *)ln.sort.desc.ensure(sizeof(uint32_t) * max_tiles);
-  J.mcount = (uint32_t *)ln.sort.mtiles.ensure(sizeof(uint32_t) * 2 * (max_seg + 1));
-  J.mbase = J.mcount + (max_seg + 1);
-  J.npass = npass;
-  J.shift = shift;
-  J.keybits = keybits;
+  J.S = g.nb;
+  J.shift = g.shift;
+  J.tcount = (uint32_t *)ln.sort.tiles.ensure(sizeof(uint32_t) * 2 * (g.max_seg + 1));
+  J.tbase = J.tcount + (g.max_seg + 1);
+  J.desc = (uint32_t *)ln.sort.desc.ensure(sizeof(uint32_t) * g.max_tiles);
+  J.mcount = (uint32_t *)ln.sort.mtiles.ensure(sizeof(uint32_t) * 2 * (g.max_seg + 1));
+  J.mbase = J.mcount + (g.max_seg + 1);
 }
 
 // passes 2 .. up to the last pass's readback (queued on the lane; no host wait)
 void bucket_sort_passes(BucketSortJob &J) {
   MsmLane &ln = *J.ln;
   hipStream_t st = ln.stream;
-  const int npass = J.npass, keybits = J.keybits, *bits = J.bits;
-  const size_t E = J.E;
+  const SortGeom &g = J.g;
   uint32_t **seg = J.seg;
-  for (int p = 1; p < npass; p++) {
+  for (int p = 1; p < g.npass; p++) {
     J.p = p;
-    J.nb = 1 << bits[p];
-    J.shift -= bits[p];
-    // 8192-entry tiles, except a last pass whose segments average <= 3584 entries (4096: the
-    // one-tile segments fill it, and half the LDS doubles the blocks per CU -- pass 3 of a 2^24
-    // opening MSM 1.02 -> 0.61 ms, profiles/r02_ab_sort_tiles.txt)
-    const int tile = (p == npass - 1 && (E >> (keybits - bits[p])) <= 3584) ? 4096 : BS_TILE;
-    J.tile = tile;
+    J.nb = 1 << g.bits[p];
+    J.shift -= g.bits[p];
+    const int tile = J.tile = g.tile[p];
     // In the last pass most segments fit one tile and rank locally; only segments of >= 2
     // tiles need the histogram pass and the global scan, so their counts get a compact layout,
     // sized from a readback of the tile totals (the top window's narrow digits make the
     // low-magnitude buckets' segments multi-tile).  All one-tile: no geometry at all (at 2^24
     // the full layout's histograms and scan over 512 bins x every tile took 0.34 ms).
-    J.last = p == npass - 1;
-    if (J.S + 1 <= SCAN_SMALL) {  // the tile geometry in one launch (k_bs_geom)
+    const bool last = p == g.npass - 1;
+    if (g.one_launch[p]) {  // the tile geometry in one launch (k_bs_geom)
       uint32_t *pub = nullptr, *flag = nullptr, seq = 0;
-      if (J.last) lane_publish_slot(ln, LANE_SLOT_SORT, &pub, &flag, &seq);
-      k_bs_geom<<<1, ONE_BLOCK, 0, st>>>(seg[J.cur], J.S, (uint32_t)tile, J.tbase, J.last ? J.mbase : nullptr, J.valid,
+      if (last) lane_publish_slot(ln, LANE_SLOT_SORT, &pub, &flag, &seq);
+      k_bs_geom<<<1, ONE_BLOCK, 0, st>>>(seg[J.cur], J.S, (uint32_t)tile, J.tbase, last ? J.mbase : nullptr, J.valid,
                                     pub, flag, seq);
       TNS_LAUNCH_CHECK();
-      if (J.last) {
+      if (last) {
         J.pending = true;
         return;
       }
@@ -1015,10 +904,10 @@ void bucket_sort_passes(BucketSortJob &J) {
       continue;
     }
     k_bs_tiles<<<grid_for(J.S + 1, 256), 256, 0, st>>>(seg[J.cur], J.S, (uint32_t)tile, J.tcount,
-                                                         J.last ? J.mcount : nullptr);
+                                                         last ? J.mcount : nullptr);
     TNS_LAUNCH_CHECK();
     exclusive_scan(st, ln.sort.scan, J.tcount, J.tbase, J.S + 1);
-    if (J.last) {  // the readback; pass_rest runs after bucket_sort_finish's wait
+    if (last) {  // the readback; pass_rest runs after bucket_sort_finish's wait
       exclusive_scan(st, ln.sort.scan, J.mcount, J.mbase, J.S + 1);
       // (with the entry count k_bs_segs1 wrote: the accumulation sizes its chunks from it)
       const void *src[3] = {J.tbase + J.S, J.mbase + J.S, J.valid};
@@ -1036,11 +925,12 @@ void bucket_sort_passes(BucketSortJob &J) {
 void bucket_sort_pass_rest(BucketSortJob &J, bool readback) {
   MsmLane &ln = *J.ln;
   hipStream_t st = ln.stream;
+  const SortGeom &g = J.g;
   const int nb = J.nb, tile = J.tile, cur = J.cur;
   const size_t S = J.S;
   int ident = 0;
   const uint32_t *mb = nullptr;
-  size_t tiles_bound = (J.E + tile - 1) / tile + S, scan_len = (size_t)nb * tiles_bound + 1;
+  size_t tiles_bound = (g.E + tile - 1) / tile + S, scan_len = (size_t)nb * tiles_bound + 1;
   if (readback) {
     const uint32_t *h = (const uint32_t *)J.readback;
     ident = h[1] == 0;
@@ -1053,10 +943,10 @@ void bucket_sort_pass_rest(BucketSortJob &J, bool readback) {
     TNS_LAUNCH_CHECK();
   }
   // packed tail: pass npass - 2 writes packed words, the last pass bins them by their top bits
-  const int pk = J.pk ? (J.p == J.npass - 2 ? 1 : J.p == J.npass - 1 ? 2 : 0) : J.vo && J.p == J.npass - 1 ? 3 : 0;
-  const PackArgs PA{J.ibits, J.bits[J.npass - 1], J.wb, J.shared ? 1 : 0, J.stride};
-  const int kin = J.kf[J.p - 1], kout = J.p < J.npass - 1 ? J.kf[J.p] : KF_U32;
-  PassGeom G{J.seg[cur], J.tbase, J.desc, pk == 2 ? J.ibits + 1 : J.shift, nb, (uint32_t)nb - 1, ident, mb, kin,
+  const int pk = g.pk ? (J.p == g.npass - 2 ? 1 : J.p == g.npass - 1 ? 2 : 0) : g.vo && J.p == g.npass - 1 ? 3 : 0;
+  const PackArgs PA{g.ibits, g.bits[g.npass - 1], g.wb, g.plan.shared ? 1 : 0, g.plan.stride};
+  const int kin = g.kf[J.p - 1], kout = J.p < g.npass - 1 ? g.kf[J.p] : KF_U32;
+  PassGeom G{J.seg[cur], J.tbase, J.desc, pk == 2 ? g.ibits + 1 : J.shift, nb, (uint32_t)nb - 1, ident, mb, kin,
              pk == 0 ? kout : KF_U32};
   uint32_t *counts = J.counts, *offs = J.offs;
   if (!ident) {
@@ -1095,13 +985,13 @@ BucketOrder bucket_sort_finish(BucketSortJob &J) {
     bucket_sort_pass_rest(J, true);
   }
   uint32_t *bstart = J.seg[J.cur];
-  if (J.wb) {  // (bucket, window) segments -> bucket starts
+  if (J.g.wb) {  // (bucket, window) segments -> bucket starts
     bstart = J.seg[J.cur ^ 1];
-    const size_t nbk = (size_t)1 << J.bucket_bits;
-    k_bs_bucket_starts<<<grid_for(nbk + 1, 256), 256, 0, ln.stream>>>(J.seg[J.cur], nbk, J.wb, bstart);
+    const size_t nbk = (size_t)1 << J.g.plan.bucket_bits;
+    k_bs_bucket_starts<<<grid_for(nbk + 1, 256), 256, 0, ln.stream>>>(J.seg[J.cur], nbk, J.g.wb, bstart);
     TNS_LAUNCH_CHECK();
   }
-  return BucketOrder{J.vo ? nullptr : J.K[J.cur], J.V[J.cur], bstart, J.wb, entries};
+  return BucketOrder{J.g.vo ? nullptr : J.K[J.cur], J.V[J.cur], bstart, J.g.wb, entries};
 }
 
 // The opening quotients (lagrange.hip k_node_quotient2_canon<true>) fused with both sorts' pass-1
@@ -1142,10 +1032,11 @@ __global__ void __launch_bounds__(BS_BLOCK) k_quotient2_count1(const Fr *__restr
 }
 
 bool quotient2_count_dev(Ctx *c, const Fr *y0, const Fr *y1, size_t n, const Fr &v0, const Fr &v1, const Fr *inv,
-                         Fr *q0, Fr *q1, unsigned *bits, int cw, int W, const uint32_t *counts_out[2]) {
-  if (cw != 22 || W != 12) return false;  // (the openings' table plan at 2^21..2^26 nodes; else unfused)
-  const Pass1Geom g = pass1_geom(n, cw, W, true, cw - 1);
-  if (!g.ct || g.npass < 2) return false;
+                         Fr *q0, Fr *q1, unsigned *bits, const WindowPlan &plan, const uint32_t *counts_out[2]) {
+  // (the openings' table plan at 2^21..2^26 nodes; else unfused)
+  if (plan.c != 22 || plan.W != 12 || !plan.shared) return false;
+  const SortGeom g = sort_geom(n, plan);
+  if (g.ct < 0 || g.npass < 2) return false;
   uint32_t *cnt[2];
   for (int k = 0; k < 2; k++) cnt[k] = (uint32_t *)c->lanes[k].sort.counts.ensure(sizeof(uint32_t) * g.cnt_len);
   TNS_PROF(c, "open_scan", 32.0 * 5 * n);
@@ -1158,29 +1049,19 @@ bool quotient2_count_dev(Ctx *c, const Fr *y0, const Fr *y1, size_t n, const Fr 
   return true;
 }
 
-bool bucket_sort_precount_bits(MsmLane &ln, const Fr *scalars, size_t n, int c, int W, bool shared, int bucket_bits,
-                               unsigned *bits, SortInput &in, bool want_low64) {
-  const Pass1Geom g = pass1_geom(n, c, W, shared, bucket_bits);
-  if (!g.ct) return false;
+bool bucket_sort_precount_bits(MsmLane &ln, const Fr *scalars, size_t n, const WindowPlan &plan, unsigned *bits,
+                               SortInput &in, bool want_low64) {
+  const SortGeom g = sort_geom(n, plan);
+  if (g.ct < 0) return false;
   uint32_t *counts = (uint32_t *)ln.sort.counts.ensure(sizeof(uint32_t) * g.cnt_len);
   uint64_t *low = want_low64 ? (uint64_t *)ln.sort.low64.ensure(sizeof(uint64_t) * n) : nullptr;
-  DigitArgs A{scalars, n, g.spb, c, W, g.wb, shared, 0u, true, nullptr, 0};
-  g.ct->count<<<(unsigned)g.T1, BS_BLOCK, 0, ln.stream>>>(A, g.shift, g.nb, g.T1, counts, bits, low);
+  DigitArgs A{scalars, n, g.spb, plan.c, plan.W, g.wb, plan.shared, 0u, true, nullptr, 0};
+  kPass1Kernels[g.ct].count<<<(unsigned)g.T1, BS_BLOCK, 0, ln.stream>>>(A, g.shift, g.nb, g.T1, counts, bits, low);
   TNS_LAUNCH_CHECK();
   in.low64 = low;
   in.precounted = counts;
-  in.pre_c = c;
-  in.pre_W = W;
-  in.pre_shared = shared;
+  in.pre = plan;
   return true;
-}
-
-BucketOrder bucket_sort_dev(MsmLane &ln, const SortInput &in, size_t n, int c, int W, bool shared, uint32_t stride,
-                            int bucket_bits, uint32_t *valid) {
-  BucketSortJob J;
-  bucket_sort_begin(ln, in, n, c, W, shared, stride, bucket_bits, valid, J);
-  bucket_sort_passes(J);
-  return bucket_sort_finish(J);
 }
 
 }  // namespace tns

@@ -194,8 +194,11 @@ void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const F
   const FixedBase *f0 = p0.basis->fb.get(), *f1 = p1.basis->fb.get();
   const uint32_t *pre[2] = {nullptr, nullptr};
   bool fused = false;
-  if (same_nodes && canon_inv && c->msm_tables && f0 && f1 && f0->c == f1->c && f0->W == f1->W)
-    fused = quotient2_count_dev(c, p0.y, p1.y, p0.cnt, value[0], value[1], q1, q0, q1, qbits, f0->c, f0->W, pre);
+  WindowPlan full;
+  if (same_nodes && canon_inv && c->msm_tables && f0 && f1 && f0->c == f1->c && f0->W == f1->W) {
+    full = WindowPlan{f0->c, f0->W, true, f0->c - 1, 0u};  // (the counts do not depend on the table's stride)
+    fused = quotient2_count_dev(c, p0.y, p1.y, p0.cnt, value[0], value[1], q1, q0, q1, qbits, full, pre);
+  }
   if (fused) {
   } else if (same_nodes) {
     lagrange_quotient_finish2_dev(c, p0.y, p1.y, p0.cnt, value[0], value[1], q1, q0, q1, qbits, canon_inv);
@@ -211,8 +214,7 @@ void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const F
   if (fused) {  // (lane 0 sorts a0, lane 1 a1: neither is late)
     a0.precounted = pre[0];
     a1.precounted = pre[1];
-    a0.pre_c = a1.pre_c = f0->c;
-    a0.pre_W = a1.pre_W = f0->W;
+    a0.pre = a1.pre = full;
     a0.plan_bits = a1.plan_bits = 254;  // (the counts assumed the full-width table plan)
   }
   msm_pair_dev(c, a0, a1, pp);

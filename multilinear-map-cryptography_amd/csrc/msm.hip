@@ -43,68 +43,6 @@ namespace tns {
 
 constexpr int RED_L = 16;  // running-sum group size of the bucket reduction
 
-struct MsmPlan {
-  bool shared = false;  // fixed-base shared-bucket layout
-  int c = 0, W = 0, wbits = 0;
-  uint32_t sentinel = 0;
-  int end_bit = 0;
-  size_t nb = 0;      // buckets in total
-  int Wr = 0;         // bucket sets (windows) to reduce: W (per-window) or 1 (shared)
-  size_t half = 0;    // buckets per set, 2^(c-1)
-  size_t stride = 0;  // shared: table stride n_table (value = j * stride + i)
-};
-
-// signed-digit windows of c bits for `bits`-bit scalars: the top window's raw value
-// < 2^(bits - c(W-1)) must stay <= 2^(c-1) so that it never carries out
-static int windows_for(int bits, int c) {
-  int W = (bits + c - 1) / c;
-  if (bits - c * (W - 1) > c - 1) W++;
-  return W;
-}
-
-// bucket additions + ~3 additions per bucket in the reduction
-static double plan_cost(size_t n, int W, int c, int sets) {
-  return (double)W * (double)n + 3.0 * sets * (double)((size_t)1 << (c - 1));
-}
-
-// w1max > cmax: scalars of up to w1max - 1 bits may also take one window of bits + 1 (no
-// second window for the signed digits' carry, e.g. 22-bit trace addresses: n additions
-// instead of 2n, and no thousands-deep buckets)
-// tie: a window must cost below tie x the best smaller one to be taken (0.98: near-ties go to the
-// smaller window, less bucket memory)
-static int best_window(size_t n, int bits, int cmax, bool shared, int w1max = 0, double tie = 0.98) {
-  int lg = 0;
-  while (((size_t)1 << lg) < n) lg++;
-  double best = 1e300;
-  int bc = 4;
-  for (int c = 4; c <= cmax && c <= lg + 2; c++) {
-    const int W = windows_for(bits, c);
-    const double cost = plan_cost(n, W, c, shared ? 1 : W);
-    if (cost < best * tie) {
-      best = cost;
-      bc = c;
-    }
-  }
-  const int c1 = bits + 1;
-  if (c1 > cmax && c1 <= w1max && c1 <= lg + 2 && plan_cost(n, 1, c1, 1) < best * tie) bc = c1;
-  return bc;
-}
-
-static void finish_plan(MsmPlan &p) {
-  p.half = (size_t)1 << (p.c - 1);
-  if (p.shared) {
-    p.wbits = 0;
-    p.Wr = 1;
-  } else {
-    p.wbits = 0;
-    while ((1 << p.wbits) < p.W) p.wbits++;
-    p.Wr = p.W;
-  }
-  p.end_bit = p.wbits + (p.c - 1) + 1;
-  p.sentinel = 1u << (p.wbits + p.c - 1);
-  p.nb = (size_t)p.Wr * p.half;
-}
-
 // *bits = max over i of bitlen(canonical scalar_i); canon (optional) = the canonical scalars
 // (the bucket sort canonicalises Montgomery scalars itself, so the MSMs pass none)
 __global__ void __launch_bounds__(256) k_scalar_bits(const Fr *__restrict__ scalars, size_t n,
@@ -593,14 +531,6 @@ __global__ void __launch_bounds__(256) k_dbl_times(G1Xyzz *__restrict__ x, size_
   }
 }
 
-// the window a table for n points uses: the shared-layout optimum for full-width scalars
-static int table_window(size_t n) {
-  // no near-tie preference for the shared tables: at 2^20 + 1 points c = 19 (W = 14) was taken
-  // over c = 20 (W = 13, 2 % cheaper in plan_cost) and the 2^20 MSM over it ran 2.42 vs 2.01 ms
-  // (deeper buckets: 56 vs 26 entries each, k_bucket_fixup 0.28 vs 0.07 ms)
-  return best_window(n, 254, 22, true, 0, 1.0);
-}
-
 std::unique_ptr<FixedBase> fixed_base_build_dev(Ctx *c, const G1Affine *points, size_t n) {
   auto fb = std::make_unique<FixedBase>();
   fb->n = n;
@@ -660,18 +590,18 @@ static void sum_sets(hipStream_t st, G1Xyzz *X, int sets, size_t n, G1Xyzz *tmp,
   TNS_LAUNCH_CHECK();
 }
 
-// One MSM in flight on a lane: launched by msm_launch, completed by msm_complete.
+// How far an MSM has got.  msm_launch_sort leaves Immediate (n == 0, all scalars zero: the result is
+// known), Tiny (k_msm_tiny: one point in the lane's pinned buffer) or Pass1Queued; msm_sort_passes:
+// -> PassesQueued (up to the last pass's readback); msm_finish_sort: -> Sorted (the bucket order exists).
+enum class MsmStage { None, Immediate, Tiny, Pass1Queued, PassesQueued, Sorted };
+// One MSM in flight on a lane: launched by msm_launch_sort, completed by msm_complete.
 struct MsmJob {
   MsmLane *lane = nullptr;
-  bool immediate = false;  // result already known (n == 0, all scalars zero)
-  G1Xyzz result;
-  bool tiny = false;       // k_msm_tiny path: one point in the lane's pinned buffer
+  MsmStage stage = MsmStage::None;
+  bool sorted() const { return stage == MsmStage::Sorted; }
+  void expect(MsmStage s, const char *what) const { if (stage != s) throw Error(TNS_ERR_DEVICE, what); }
   MsmPlan P;
   int L0 = 0, nbits = 0, specs = 0;
-  // between the sort phase and the accumulation phase
-  bool sorted = false;
-  bool sort_pending = false;        // bucket_sort_begin done, msm_finish_sort not yet
-  bool passes_pending = false;      // bucket_sort_passes not yet queued
   BucketSortJob bs;
   hipEvent_t sorted_ev = nullptr;   // recorded on the lane once the bucket order exists
   std::unique_ptr<ProfScope> sort_prof;  // "msm_sort" timing from pass 1 to the last pass
@@ -776,9 +706,8 @@ static SortInput bits_launch(MsmLane &ln, const Fr *scalars, size_t n) {
   in.mont = true;
   const MsmLane::PlanHint &h = ln.hint;
   // (narrow per-window plans -- the trace values -- also get their canonical low 64 bits written)
-  const bool narrow = !h.shared && h.c * h.W <= 64;
-  if (!(h.n == n && h.c > 0 &&
-        bucket_sort_precount_bits(ln, scalars, n, h.c, h.W, h.shared, h.bucket_bits, d_bits, in, narrow))) {
+  const bool narrow = !h.plan.shared && h.plan.c * h.plan.W <= 64;
+  if (!(h.n == n && h.plan.c > 0 && bucket_sort_precount_bits(ln, scalars, n, h.plan, d_bits, in, narrow))) {
     k_scalar_bits<<<grid_for(n, 256, 2048), 256, 0, ln.stream>>>(scalars, n, d_bits, nullptr);
     TNS_LAUNCH_CHECK();
   }
@@ -789,6 +718,34 @@ static SortInput bits_launch(MsmLane &ln, const Fr *scalars, size_t n) {
 }
 
 static unsigned bits_result(MsmLane &ln) { return *(const unsigned *)lane_wait(ln, LANE_SLOT_BITS); }
+
+// An MSM's first step on its lane: the scalars' prep, then their bit length on its way to the host
+// (computed here for Montgomery scalars; canonical inputs -- the opening quotients -- and raw u64
+// inputs -- trace addresses, lookup indices -- come with theirs).  Returns what the sort will read.
+static SortInput msm_prepare_scalars(MsmLane &ln, const MsmArgs &x) {
+  if (x.src.prep) x.src.prep(ln.stream);
+  if (x.n <= 64) return SortInput();
+  if (!x.src.canon_bits) return bits_launch(ln, x.scalars, x.n);
+  if (x.plan_bits <= 0) {  // (plan_bits: nothing to read back)
+    const void *src[1] = {x.src.canon_bits};
+    const size_t by[1] = {sizeof(unsigned)};
+    lane_publish(ln, LANE_SLOT_BITS, 1, src, by);
+  }
+  SortInput in;
+  if (x.src.u64) {
+    in.u64 = x.src.u64;
+    in.n_u64 = x.src.n_u64;
+  } else {
+    in.fr = x.src.canon ? x.src.canon : x.scalars;
+    in.precounted = x.precounted;
+    in.pre = x.pre;
+  }
+  return in;
+}
+// the bit length msm_prepare_scalars put on its way (a host wait, unless the caller fixed it)
+static unsigned msm_bits(MsmLane &ln, const MsmArgs &x) {
+  return x.n <= 64 ? 254u : x.plan_bits > 0 ? (unsigned)x.plan_bits : bits_result(ln);
+}
 
 // Entries per accumulation thread.  Per-window plans (the narrow commitments: runs of a few
 // entries, flush- and latency-bound): 128, halved down to 32 while the MSM gives fewer than
@@ -818,92 +775,76 @@ static int acc_chunk(Ctx *ctx, size_t entries, bool table_plan) {
 // Phase 1 on lane `ln` (asynchronous): plan, digits and the bucket order.  Trivial cases
 // (all scalars zero, n <= 64) finish here.  `sorted` (optional) is recorded on the lane once
 // the bucket order exists (or right away when there is none).
-// canon: the canonical scalars from bits_launch (n > 64).
-// defer: stop before the bucket sort's host wait (its last pass's readback); msm_finish_sort
-// completes it, so a pair of MSMs can queue both lanes' passes before either waits.
+// in, bits: from msm_prepare_scalars and msm_bits.  defer: stop after pass 1; msm_sort_passes and
+// msm_finish_sort (the sort's host wait) complete it, so a pair queues both lanes' passes before either waits.
+struct SortOptions {
+  hipEvent_t sorted = nullptr;
+  bool defer = false;
+};
+static void msm_sort_passes(MsmJob &J);
 static void msm_finish_sort(MsmJob &J);
-static void msm_launch_sort(Ctx *ctx, MsmLane &ln, const G1Affine *points, const Fr *scalars, const SortInput &in,
-                            size_t n, const FixedBase *fb, unsigned bits, MsmJob &J, hipEvent_t sorted = nullptr,
-                            bool defer = false, size_t fb_off = 0) {
+static void msm_launch_sort(Ctx *ctx, MsmLane &ln, const MsmArgs &x, const SortInput &in, unsigned bits, MsmJob &J,
+                            const SortOptions &opt = SortOptions()) {
+  J.expect(MsmStage::None, "MSM job launched twice");
+  const size_t n = x.n;
   J.lane = &ln;
   J.ctx = ctx;
-  J.sorted_ev = sorted;
   hipStream_t st = ln.stream;
-  auto record_now = [&]() {
-    if (J.sorted_ev) TNS_HIP(hipEventRecord(J.sorted_ev, st));
-    J.sorted_ev = nullptr;
+  auto record_now = [&]() {  // (no bucket order to wait for)
+    if (opt.sorted) TNS_HIP(hipEventRecord(opt.sorted, st));
   };
   if (n == 0 || bits == 0) {  // all scalars zero
-    J.immediate = true;
-    J.result = G1Xyzz::inf();
+    J.stage = MsmStage::Immediate;
     record_now();
     return;
   }
   if (n <= 64) {
     G1Xyzz *d = (G1Xyzz *)ln.msm.tiny_out.ensure(sizeof(G1Xyzz));
-    k_msm_tiny<<<1, 64, 0, st>>>(points, scalars, (int)n, d);
+    k_msm_tiny<<<1, 64, 0, st>>>(x.points, x.scalars, (int)n, d);
     TNS_LAUNCH_CHECK();
     const void *src[1] = {d};
     const size_t by[1] = {sizeof(G1Xyzz)};
     lane_publish(ln, LANE_SLOT_SUMS, 1, src, by);
-    J.tiny = true;
+    J.stage = MsmStage::Tiny;
     record_now();
     return;
   }
   if (n >= ((size_t)1 << 31)) throw Error(TNS_ERR_COMMITMENT, "MSM larger than 2^31 points");
 
-  // plan: per-window layout, or the shared layout when a fixed-base table covers the points
-  MsmPlan &P = J.P;
-  P = MsmPlan();
-  P.c = best_window(n, (int)bits, 20, false, 23);
-  P.W = windows_for((int)bits, P.c);
-  if (fb && ctx->msm_tables && fb->n >= fb_off + n && (uint64_t)fb->n * fb->W < ((uint64_t)1 << 31)) {
-    const int Ws = windows_for((int)bits, fb->c);
-    if (Ws <= fb->W && plan_cost(n, Ws, fb->c, 1) < plan_cost(n, P.W, P.c, P.W)) {
-      P.shared = true;
-      P.c = fb->c;
-      P.W = Ws;
-      P.stride = fb->n;
-      points = fb->table.as<G1Affine>() + fb_off;  // T[w n + fb_off + i]: value w stride + i
-    }
-  }
-  finish_plan(P);
-  if (in.mont && in.fr && !in.u64) ln.hint = MsmLane::PlanHint{n, P.c, P.W, P.end_bit - 1, P.shared};
-  SortInput in2 = in;
-  if (in.low64 && bits <= 64) {  // the scalars fit 64 bits: the sort reads their canonical low words
-    in2.u64 = in.low64;
-    in2.n_u64 = n;
-    in2.fr = nullptr;
-    in2.mont = false;
-  }
+  const FixedBase *fb = x.fb;
+  const TableShape table = fb ? TableShape{fb->n, fb->c, fb->W} : TableShape();
+  const MsmPlan &P = J.P = plan_msm(n, (int)bits, table, x.fb_off, ctx->msm_tables);
+  // (plan_msm: the shared layout when a fixed-base table covers the points -- T[w n + fb_off + i]: value w stride + i)
+  J.points = P.shared ? fb->table.as<G1Affine>() + x.fb_off : x.points;
+  if (in.mont && in.fr && !in.u64) ln.hint = MsmLane::PlanHint{n, P};
   const size_t total = (size_t)P.W * n;
   if (total >= ((size_t)1 << 31)) throw Error(TNS_ERR_COMMITMENT, "MSM too large for one sort");
 
-  const int acc_k = acc_chunk(ctx, total, false);  // from the bound; table plans refine it from the sort's count
-  J.points = points;
-  J.acc_k = acc_k;
-  J.nchunks = (total + acc_k - 1) / acc_k;
+  J.acc_k = acc_chunk(ctx, total, false);  // from the bound; table plans refine it from the sort's count
+  J.nchunks = (total + J.acc_k - 1) / J.acc_k;
   J.n = n;
   J.sort_prof.reset(new ProfScope(ctx->prof, st, "msm_sort", 32.0 * n + 16.0 * total));
   J.valid = (uint32_t *)ln.msm.words.ensure(2 * sizeof(uint32_t));  // entries; [1]: a run crosses a chunk
-  bucket_sort_begin(ln, in2, n, P.c, P.W, P.shared, (uint32_t)P.stride, P.end_bit - 1, J.valid, J.bs);
-  J.sort_pending = true;
-  J.passes_pending = true;
-  if (!defer) msm_finish_sort(J);
+  bucket_sort_begin(ln, sort_input_for_bits(in, n, bits), n, P, J.valid, J.bs);
+  J.sorted_ev = opt.sorted;
+  J.stage = MsmStage::Pass1Queued;
+  if (opt.defer) return;
+  msm_sort_passes(J);
+  msm_finish_sort(J);
 }
 
 // the bucket sort's passes after pass 1, up to the last pass's readback (no host wait)
 static void msm_sort_passes(MsmJob &J) {
-  if (!J.passes_pending) return;
-  J.passes_pending = false;
+  if (J.stage == MsmStage::Immediate || J.stage == MsmStage::Tiny) return;  // nothing to sort
+  J.expect(MsmStage::Pass1Queued, "MSM sort passes without pass 1");
   bucket_sort_passes(J.bs);
+  J.stage = MsmStage::PassesQueued;
 }
 
 // the bucket sort's last stage (waits for its last-pass readback), then the sorted state
 static void msm_finish_sort(MsmJob &J) {
-  if (!J.sort_pending) return;
-  msm_sort_passes(J);
-  J.sort_pending = false;
+  if (J.stage == MsmStage::Immediate || J.stage == MsmStage::Tiny) return;
+  J.expect(MsmStage::PassesQueued, "MSM sort finished before its passes");
   const BucketOrder o = bucket_sort_finish(J.bs);
   J.sort_prof.reset();  // the stage's end event, after the last pass on the lane
   if (o.entries != SIZE_MAX && J.P.shared) {  // table plans: chunks sized from the actual entry count
@@ -915,7 +856,7 @@ static void msm_finish_sort(MsmJob &J) {
   J.bstart = o.bstart;
   J.bend = o.bstart + 1;
   J.ks = o.ks;
-  J.sorted = true;
+  J.stage = MsmStage::Sorted;
   if (J.sorted_ev) TNS_HIP(hipEventRecord(J.sorted_ev, J.lane->stream));
   J.sorted_ev = nullptr;
 }
@@ -923,7 +864,7 @@ static void msm_finish_sort(MsmJob &J) {
 // Phase 2 (asynchronous): accumulation, bucket fixup, reduction and the per-set sums' readback.
 // `accumulated` (optional) is recorded on the lane right after the accumulation kernel.
 static void msm_launch_accumulate(Ctx *ctx, MsmJob &J, hipEvent_t accumulated, hipStream_t on = nullptr) {
-  if (!J.sorted) {  // immediate / tiny: done in phase 1
+  if (!J.sorted()) {  // immediate / tiny: done in phase 1
     if (accumulated) TNS_HIP(hipEventRecord(accumulated, on ? on : J.lane->stream));
     return;
   }
@@ -947,7 +888,7 @@ static void msm_launch_accumulate(Ctx *ctx, MsmJob &J, hipEvent_t accumulated, h
 
 // two sorted MSMs whose tails can run as one two-set launch sequence: the same bucket-set shape
 static bool same_tail_shape(const MsmJob &a, const MsmJob &b) {
-  return a.sorted && b.sorted && a.P.shared == b.P.shared && a.P.Wr == b.P.Wr && a.P.half == b.P.half;
+  return a.sorted() && b.sorted() && a.P.shared == b.P.shared && a.P.Wr == b.P.Wr && a.P.half == b.P.half;
 }
 
 // The accumulation's tail -- bucket fixup, reduction and the per-set sums' readback -- for nj = 1
@@ -961,7 +902,7 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     J[j]->res_set = j;
     J[j]->res_sets = nj;
   }
-  if (!J[0]->sorted) return;
+  if (!J[0]->sorted()) return;
   hipStream_t st = run.stream;
   const MsmPlan &P = J[0]->P;
   if (nj == 2 && (!same_tail_shape(*J[0], *J[1]) || J[1]->buckets != J[0]->buckets + P.nb))
@@ -1061,18 +1002,12 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
   }
 }
 
-static void msm_launch_reduce(Ctx *ctx, MsmJob &J, hipEvent_t accumulated = nullptr) {
-  msm_launch_accumulate(ctx, J, accumulated);
-  MsmJob *one[1] = {&J};
-  msm_launch_tails(ctx, one, 1, *J.lane);
-}
-
 // Wait for the tail's readback and finish on the host: R = sum_g T_g + L0 * sum_b 2^b M_b per
 // set, then Horner over the windows (per-window layout).
 static G1Xyzz msm_complete(Ctx *ctx, MsmJob &J) {
-  if (J.immediate) return J.result;
+  if (J.stage == MsmStage::Immediate) return G1Xyzz::inf();
   const void *hp = lane_wait(J.res_lane ? *J.res_lane : *J.lane, LANE_SLOT_SUMS);
-  if (J.tiny) return *(const G1Xyzz *)hp;
+  if (J.stage == MsmStage::Tiny) return *(const G1Xyzz *)hp;
   const MsmPlan &P = J.P;
   const G1Xyzz *all = (const G1Xyzz *)hp;
   const G1Xyzz *fin = all + (size_t)J.res_set * P.Wr * J.specs;
@@ -1095,18 +1030,20 @@ static G1Xyzz msm_complete(Ctx *ctx, MsmJob &J) {
   return acc;
 }
 
+// a whole MSM queued on a lane (one host wait for the bit length, one inside the sort) for msm_complete
+static void msm_queue_whole(Ctx *ctx, MsmLane &ln, const MsmArgs &x, MsmJob &J) {
+  const SortInput in = msm_prepare_scalars(ln, x);
+  const unsigned bits = msm_bits(ln, x);
+  msm_launch_sort(ctx, ln, x, in, bits, J);
+  msm_launch_accumulate(ctx, J, nullptr);
+  MsmJob *one[1] = {&J};
+  msm_launch_tails(ctx, one, 1, ln);
+}
+
 G1Xyzz msm_dev(Ctx *ctx, const G1Affine *points, const Fr *scalars, size_t n, const FixedBase *fb, size_t fb_off) {
   if (n == 0) return G1Xyzz::inf();
-  MsmLane &ln = ctx->lanes[0];
-  unsigned bits = 254;
-  SortInput in;
-  if (n > 64) {
-    in = bits_launch(ln, scalars, n);
-    bits = bits_result(ln);
-  }
   MsmJob J;
-  msm_launch_sort(ctx, ln, points, scalars, in, n, fb, bits, J, nullptr, false, fb_off);
-  msm_launch_reduce(ctx, J);
+  msm_queue_whole(ctx, ctx->lanes[0], MsmArgs{points, scalars, n, fb, fb_off}, J);
   return msm_complete(ctx, J);
 }
 
@@ -1121,40 +1058,12 @@ static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz 
   MsmLane &l0 = ctx->lanes[0], &l1 = ctx->lanes[1];
   // lane 1 starts after everything already queued on the context stream (its inputs)
   stream_wait(l1.stream, ctx->stream);
-  unsigned ba = 254, bb = 254;
-  SortInput ca, cb;
-  // canonical inputs (the opening quotients) and raw u64 inputs (trace addresses, lookup
-  // indices) come with their bit lengths on the device
-  auto start = [&](MsmLane &ln, const MsmArgs &x) -> SortInput {
-    if (x.src.prep) x.src.prep(ln.stream);
-    if (x.n <= 64) return SortInput();
-    if (!x.src.canon_bits) return bits_launch(ln, x.scalars, x.n);
-    if (x.plan_bits <= 0) {  // (plan_bits: nothing to read back)
-      const void *src[1] = {x.src.canon_bits};
-      const size_t by[1] = {sizeof(unsigned)};
-      lane_publish(ln, LANE_SLOT_BITS, 1, src, by);
-    }
-    SortInput in;
-    if (x.src.u64) {
-      in.u64 = x.src.u64;
-      in.n_u64 = x.src.n_u64;
-    } else {
-      in.fr = x.src.canon ? x.src.canon : x.scalars;
-      in.precounted = x.precounted;
-      in.pre_c = x.pre_c;
-      in.pre_W = x.pre_W;
-    }
-    return in;
-  };
   MsmJob ja, jb;
   if (b.src.late) {
     // b's scalars are still being uploaded (HostUpload, a helper thread): a's MSM is queued whole
     // first -- sort, accumulation, tail -- so it runs under the upload; b's prep then waits for
     // the upload and b's MSM follows on lane 1
-    ca = start(l0, a);
-    if (a.n > 64) ba = bits_result(l0);
-    msm_launch_sort(ctx, l0, a.points, a.scalars, ca, a.n, a.fb, ba, ja);
-    msm_launch_reduce(ctx, ja);
+    msm_queue_whole(ctx, l0, a, ja);
     if (b.src.chunks > 1) {  // one MSM per uploaded chunk, each as soon as it lands
       const ScalarSource &bs = b.src;
       if ((int)bs.chunk_off.size() != bs.chunks + 1 || bs.chunk_off.back() != b.n)
@@ -1163,39 +1072,30 @@ static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz 
       for (int k = 0; k < bs.chunks; k++) {
         const size_t off = bs.chunk_off[k], cnt = bs.chunk_off[k + 1] - off;
         if (!cnt) continue;
-        MsmArgs bk{b.points + off, b.scalars + off, cnt, b.fb};  // (Montgomery scalars: no canon_bits)
+        MsmArgs bk{b.points + off, b.scalars + off, cnt, b.fb, off};  // (Montgomery scalars: no canon_bits)
         bk.src.prep = [&bs, k](hipStream_t s) { bs.chunk_prep(k, s); };
         MsmJob jk;
-        unsigned bk_bits = 254;
-        const SortInput ck = start(l1, bk);
-        if (cnt > 64) bk_bits = bits_result(l1);
-        msm_launch_sort(ctx, l1, bk.points, bk.scalars, ck, cnt, b.fb, bk_bits, jk, nullptr, false, off);
-        msm_launch_reduce(ctx, jk);
+        msm_queue_whole(ctx, l1, bk, jk);
         acc = xyzz_add(acc, msm_complete(ctx, jk));  // the lane's host buffer serves the next chunk
       }
       out[0] = msm_complete(ctx, ja);
       out[1] = acc;
       return;
     }
-    cb = start(l1, b);
-    if (b.n > 64) bb = bits_result(l1);
-    msm_launch_sort(ctx, l1, b.points, b.scalars, cb, b.n, b.fb, bb, jb);
-    msm_launch_reduce(ctx, jb);
+    msm_queue_whole(ctx, l1, b, jb);
     out[0] = msm_complete(ctx, ja);
     out[1] = msm_complete(ctx, jb);
     return;
   }
-  ca = start(l0, a);
-  cb = start(l1, b);
-  if (a.n > 64) ba = a.plan_bits > 0 ? (unsigned)a.plan_bits : bits_result(l0);
-  if (b.n > 64) bb = b.plan_bits > 0 ? (unsigned)b.plan_bits : bits_result(l1);
+  const SortInput ca = msm_prepare_scalars(l0, a), cb = msm_prepare_scalars(l1, b);
+  const unsigned ba = msm_bits(l0, a), bb = msm_bits(l1, b);
   Event sa, sb;
   // both lanes' passes are queued before either lane's host wait (the last pass's readback), and
   // each lane's last pass follows its own readback: the two sorts run side by side and neither
   // waits for the other's first passes (profiles/r02_ab_sort_overlap.txt, r05_ab_sort_overlap.txt)
-  msm_launch_sort(ctx, l0, a.points, a.scalars, ca, a.n, a.fb, ba, ja, sa, true);
+  msm_launch_sort(ctx, l0, a, ca, ba, ja, SortOptions{sa, true});
   msm_sort_passes(ja);
-  msm_launch_sort(ctx, l1, b.points, b.scalars, cb, b.n, b.fb, bb, jb, sb, true);
+  msm_launch_sort(ctx, l1, b, cb, bb, jb, SortOptions{sb, true});
   msm_sort_passes(jb);
   // Both accumulations go on the context's accumulation stream (ctx->acc, at the least priority:
   // api.hip's create_streams), one after the other (each is VALU-bound on the whole chip: run together
@@ -1212,11 +1112,11 @@ static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz 
   msm_finish_sort(ja);
   Event acc_a, acc_b;
   // a two-set tail needs the pair's buckets adjoining: room for both before acc a writes the first
-  if (ja.sorted && ja.P.shared) ja.buckets = (G1Xyzz *)l0.msm.buckets.ensure(sizeof(G1Xyzz) * 2 * ja.P.nb);
+  if (ja.sorted() && ja.P.shared) ja.buckets = (G1Xyzz *)l0.msm.buckets.ensure(sizeof(G1Xyzz) * 2 * ja.P.nb);
   TNS_HIP(hipStreamWaitEvent(as, sa, 0));
   msm_launch_accumulate(ctx, ja, acc_a, as);
   msm_finish_sort(jb);
-  const bool tails_last = ja.sorted && jb.sorted && ja.P.shared && jb.P.shared;
+  const bool tails_last = ja.sorted() && jb.sorted() && ja.P.shared && jb.P.shared;
   const bool two_set = tails_last && same_tail_shape(ja, jb);
   if (two_set) jb.buckets = ja.buckets + ja.P.nb;
   TNS_HIP(hipStreamWaitEvent(as, sb, 0));
@@ -1233,7 +1133,7 @@ static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz 
   }
   // two tails on two lanes: the host's part (bucket-sum Horner, ~20-45 us) of whichever lands
   // first runs while the other lane's tail still runs on the device
-  if (!two_set && jb.res_lane && jb.res_lane != ja.res_lane && jb.sorted && ja.sorted) {
+  if (!two_set && jb.res_lane && jb.res_lane != ja.res_lane && jb.sorted() && ja.sorted()) {
     // (bounded: past it the plain order below, whose waits report a faulted stream)
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spin = 1; !lane_ready(*ja.res_lane, LANE_SLOT_SUMS) && !lane_ready(*jb.res_lane, LANE_SLOT_SUMS);

@@ -1,6 +1,12 @@
 // msm.hpp -- the multi-scalar multiplication (msm.hip) and its bucket sort (bucket_sort.hip): the
 // per-stream lane with its named device workspaces and host readbacks, the fixed-base window
-// table, how an MSM's scalars are described, and the two modules' entry points.
+// table, how an MSM's scalars are described, and the two modules' entry points.  The window plan
+// and the sort's geometry are decided in msm_plan.hpp.
+//
+// An MSM's scalars have three descriptions:
+//  * MsmArgs: the caller of msm_pair_dev (kzg.hip, kzg_verify.hip) fills it -- one whole MSM;
+//  * ScalarSource (MsmArgs::src): the same caller fills it -- when and in which form the scalars arrive;
+//  * SortInput: msm.hip's msm_prepare_scalars fills it from the two -- what the sort's pass 1 reads.
 #pragma once
 #include <functional>
 #include <memory>
@@ -8,6 +14,7 @@
 
 #include "bn254.hpp"
 #include "hip_util.hpp"
+#include "msm_plan.hpp"
 
 namespace tns {
 
@@ -39,12 +46,10 @@ struct SortInput {
   const uint64_t *u64 = nullptr;
   size_t n_u64 = 0;
   // set: pass 1's tile histograms are already in the lane's count buffer (SortWs::counts ==
-  // precounted), computed for the shared-table plan (pre_c, pre_W) over these n scalars
-  // (quotient2_count_dev: the opening quotients' kernel counts their digits as it writes them);
-  // another plan recounts
+  // precounted), computed for the plan `pre` over these n scalars (quotient2_count_dev: the
+  // opening quotients' kernel counts their digits as it writes them); another plan recounts
   const uint32_t *precounted = nullptr;
-  int pre_c = 0, pre_W = 0;
-  bool pre_shared = true;
+  WindowPlan pre;
   // set (with precounted, Montgomery scalars): the count kernel also wrote each scalar's canonical
   // low 64 bits here; when the bit length shows the scalars fit 64 bits the sort reads these
   // (8 bytes a scalar, no Montgomery reduction) instead of the 32-byte scalars
@@ -71,43 +76,41 @@ struct SortWs {
 // all but the wait are queued on the lane without blocking the host.
 struct BucketSortJob {
   MsmLane *ln = nullptr;
-  size_t E = 0, S = 0;
-  int bucket_bits = 0, wb = 0, npass = 0, cur = 0, nb = 0, shift = 0, tile = 0, keybits = 0;
-  int bits[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // key bits per pass
-  bool last = false, pending = false;
+  SortGeom g;
+  // what changes while the sort runs: the pass p in flight with its bins, shift and tile, the
+  // segments S before it, and which of the ping / pong buffers holds them (cur)
+  size_t S = 0;
+  int cur = 0, p = 0, nb = 0, shift = 0, tile = 0;
+  bool pending = false;            // the last pass waits for its tile totals' readback
   const void *readback = nullptr;  // the last pass's tile totals once read back (host memory)
   uint32_t *K[2] = {nullptr, nullptr}, *V[2] = {nullptr, nullptr}, *seg[2] = {nullptr, nullptr};
   uint32_t *counts = nullptr, *offs = nullptr, *tcount = nullptr, *tbase = nullptr, *desc = nullptr;
   uint32_t *mcount = nullptr, *mbase = nullptr;
   uint32_t *valid = nullptr;  // device: the entry count
-  // packed tail (pk): the second-to-last pass writes one u32 per entry -- the last pass's key
-  // bits, the sign and the point index i (ibits bits) -- and the last pass reads that word and
-  // writes the accumulation's values only (no keys: runs come from the bucket starts)
-  bool pk = false, vo = false, shared = false;  // vo: the last pass writes values only
-  int ibits = 0, p = 0;
-  uint32_t stride = 0;
-  int kf[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // key format pass p writes (bucket_sort.hip KF_*)
 };
-void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, int c, int W, bool shared, uint32_t stride,
-                       int bucket_bits, uint32_t *valid, BucketSortJob &J);
+void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, const WindowPlan &plan, uint32_t *valid,
+                       BucketSortJob &J);
 void bucket_sort_passes(BucketSortJob &J);
 void bucket_sort_pass_rest(BucketSortJob &J, bool readback);
 BucketOrder bucket_sort_finish(BucketSortJob &J);
 // The two opening MSMs' scalars q_k,i = (v_k - y_k,i) inv_i (canonical: the inverses are) with their
 // bit lengths, as lagrange_quotient_finish2_dev, AND pass 1's tile histograms of both sorts for the
-// shared-table plan (c, W) straight into lanes[0] / lanes[1]'s count buffers: the sorts skip their
-// count kernels (one read of both quotient vectors less).  false (nothing queued): no compile-time
-// pass-1 plan for (c, W) -- the caller runs the plain quotient kernel.
+// shared-table plan straight into lanes[0] / lanes[1]'s count buffers: the sorts skip their
+// count kernels (one read of both quotient vectors less).  false (nothing queued): no fused kernel
+// for the plan -- the caller runs the plain quotient kernel.
 bool quotient2_count_dev(Ctx *c, const Fr *y0, const Fr *y1, size_t n, const Fr &v0, const Fr &v1, const Fr *inv,
-                         Fr *q0, Fr *q1, unsigned *bits, int cw, int W, const uint32_t *counts_out[2]);
+                         Fr *q0, Fr *q1, unsigned *bits, const WindowPlan &plan, const uint32_t *counts_out[2]);
 // n Montgomery scalars' largest bit length (into *bits, zeroed by the caller) together with pass 1's
-// histograms for the plan (c, W, shared, bucket_bits) in the lane's count buffer; `in` then carries
-// them as precounted.  false (nothing queued): no compile-time pass-1 plan for it.
-bool bucket_sort_precount_bits(MsmLane &ln, const Fr *scalars, size_t n, int c, int W, bool shared, int bucket_bits,
-                               unsigned *bits, SortInput &in, bool want_low64);
-// both phases at once (single MSMs)
-BucketOrder bucket_sort_dev(MsmLane &ln, const SortInput &in, size_t n, int c, int W, bool shared, uint32_t stride,
-                            int bucket_bits, uint32_t *valid);
+// histograms for `plan` in the lane's count buffer; `in` then carries them as precounted.  false
+// (nothing queued): no compile-time pass-1 shape for it.
+bool bucket_sort_precount_bits(MsmLane &ln, const Fr *scalars, size_t n, const WindowPlan &plan, unsigned *bits,
+                               SortInput &in, bool want_low64);
+// What the sort reads once the scalars' bit length is known: scalars that fit 64 bits are read
+// from their canonical low words where pass 1's precount wrote them (SortInput::low64)
+inline SortInput sort_input_for_bits(SortInput in, size_t n, unsigned bits) {
+  if (in.low64 && bits <= 64) in.u64 = in.low64, in.n_u64 = n, in.fr = nullptr, in.mont = false;
+  return in;
+}
 
 // ---------------------------------------------------------------- msm.hip
 // A lane's MSM workspaces beside the sort's: written on the lane's stream (the accumulation of a
@@ -138,13 +141,12 @@ struct MsmLane {
   // tile totals, 2 the MSM's per-set sums
   MappedHostBuf mapped;
   uint32_t pub_seq = 0;
-  // the window plan this lane's last MSM of Montgomery scalars took (n, c, W, layout): the next
+  // the window plan this lane's last MSM of Montgomery scalars took, and its n: the next
   // such MSM of n scalars counts pass 1 for it while it computes the scalars' bit length, and the
   // sort uses those counts when the bit length confirms the plan (bucket_sort_precount_bits)
   struct PlanHint {
     size_t n = 0;
-    int c = 0, W = 0, bucket_bits = 0;
-    bool shared = false;
+    WindowPlan plan;
   } hint;
   uint32_t slot_seq[3] = {0, 0, 0};
 };
@@ -189,9 +191,11 @@ struct MsmArgs {
   const Fr *scalars;
   size_t n;
   const FixedBase *fb;
-  // set (with src.canon_bits, canonical scalars): pass 1's histograms are precounted (SortInput::precounted)
+  size_t fb_off = 0;  // the points are entries [fb_off, fb_off + n) of the set fb was built for
+  // set (with src.canon_bits, canonical scalars): pass 1's histograms are precounted for the plan
+  // `pre` (SortInput::precounted)
   const uint32_t *precounted = nullptr;
-  int pre_c = 0, pre_W = 0;
+  WindowPlan pre;
   // > 0: plan the MSM for scalars of this bit length without reading src.canon_bits back (the opening
   // quotients: full width -- the table plan's extra windows of a narrower quotient carry no digits,
   // so the entries are the same); the sort can be queued right behind the kernel writing the scalars

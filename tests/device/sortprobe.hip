@@ -14,12 +14,6 @@ namespace {
 
 using namespace tns;
 
-// bucket_sort.hip's geometry threshold (its TNS_SCAN_SMALL_LOG, same default and same override):
-// a pass over S segments with S + 1 above it takes k_bs_tiles + exclusive_scan, not k_bs_geom
-#ifndef TNS_SCAN_SMALL_LOG
-#define TNS_SCAN_SMALL_LOG 15
-#endif
-
 // the words of sortprobe_sort's `info`, in order
 enum {
   I_NPASS, I_BITS0, I_KF0 = I_BITS0 + 8, I_PK = I_KF0 + 8, I_VO, I_TILE, I_IDENT, I_MULTI, I_BIG_ROUTE, I_CT, I_KS,
@@ -37,7 +31,7 @@ int sortprobe_info_words() { return I_COUNT; }
 //   form 0: fr = n canonical 32-byte scalars; 1: fr = n Montgomery forms; 2: u64 = n_u64 <= n raw values
 //   precount (form 1 only) 1: first bucket_sort_precount_bits, 2: the same with want_low64; the sort
 //     then reads the SortInput it returned, its u64 low words when the bit length it wrote is <= 64
-//     (msm_launch_sort's substitution)
+//     (sort_input_for_bits, as msm_launch_sort)
 //   vals / keys: room for `cap` words each, bstart: for 2^bucket_bits + 1
 // Returns 0, a TNS_* status (every HIP error: TNS_ERR_DEVICE, the message in tns_last_error()),
 // or -1 for arguments the entry point does not take.
@@ -66,6 +60,7 @@ int sortprobe_sort(tns_ctx *ctx, int form, const void *fr, const uint64_t *u64, 
       in.fr = d;
       in.mont = form == 1;
     }
+    const WindowPlan plan{c, W, shared != 0, bucket_bits, stride};
     uint32_t *words = (uint32_t *)ln.msm.words.ensure(2 * sizeof(uint32_t));
     // whether a compile-time pass-1 plan matches (c, W): the shipped answer, from a precount of one
     // zero scalar (it queues nothing when there is none; the sort below recounts either way)
@@ -74,26 +69,21 @@ int sortprobe_sort(tns_ctx *ctx, int form, const void *fr, const uint64_t *u64, 
       TNS_HIP(hipMemsetAsync(one, 0, sizeof(Fr), st));
       TNS_HIP(hipMemsetAsync(words, 0, 2 * sizeof(uint32_t), st));
       SortInput tmp;
-      info[I_CT] = bucket_sort_precount_bits(ln, one, 1, c, W, shared != 0, bucket_bits, words, tmp, false) ? 1 : 0;
+      info[I_CT] = bucket_sort_precount_bits(ln, one, 1, plan, words, tmp, false) ? 1 : 0;
     }
-    if (precount) {  // msm.hip bits_launch, then msm_launch_sort's low64 substitution
+    if (precount) {  // msm.hip bits_launch, then msm_launch_sort's low-word substitution
       TNS_HIP(hipMemsetAsync(words, 0, sizeof(uint32_t), st));
-      const bool ok = bucket_sort_precount_bits(ln, in.fr, n, c, W, shared != 0, bucket_bits, words, in, precount == 2);
+      const bool ok = bucket_sort_precount_bits(ln, in.fr, n, plan, words, in, precount == 2);
       info[I_PRE_OK] = ok ? 1 : 0;
       uint32_t b = 0;
       TNS_HIP(hipMemcpyAsync(&b, words, sizeof b, hipMemcpyDeviceToHost, st));
       TNS_HIP(hipStreamSynchronize(st));
       info[I_PRE_BITS] = ok ? (int64_t)b : -1;
-      if (ok && in.low64 && b <= 64) {
-        in.u64 = in.low64;
-        in.n_u64 = n;
-        in.fr = nullptr;
-        in.mont = false;
-        info[I_LOW64_USED] = 1;
-      }
+      in = sort_input_for_bits(in, n, b);
+      info[I_LOW64_USED] = in.low64 && in.u64 == in.low64;
     }
     BucketSortJob J;
-    bucket_sort_begin(ln, in, n, c, W, shared != 0, stride, bucket_bits, words, J);
+    bucket_sort_begin(ln, in, n, plan, words, J);
     bucket_sort_passes(J);
     const bool pending = J.pending;
     info[I_LAST_S] = (int64_t)J.S;
@@ -101,21 +91,21 @@ int sortprobe_sort(tns_ctx *ctx, int form, const void *fr, const uint64_t *u64, 
     TNS_HIP(hipStreamSynchronize(st));
     uint32_t valid[2] = {0, 0};
     TNS_HIP(hipMemcpy(valid, words, sizeof valid, hipMemcpyDeviceToHost));
-    const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(valid[0], cap), J.E);
+    const SortGeom &sg = J.g;
+    const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(valid[0], cap), sg.E);
     if (take) TNS_HIP(hipMemcpy(vals, o.vals, sizeof(uint32_t) * take, hipMemcpyDeviceToHost));
     if (take && o.keys) TNS_HIP(hipMemcpy(keys, o.keys, sizeof(uint32_t) * take, hipMemcpyDeviceToHost));
     TNS_HIP(hipMemcpy(bstart, o.bstart, sizeof(uint32_t) * (((size_t)1 << bucket_bits) + 1), hipMemcpyDeviceToHost));
-    info[I_NPASS] = J.npass;
-    size_t S = 1;
+    info[I_NPASS] = sg.npass;
     for (int p = 0; p < 8; p++) {
-      info[I_BITS0 + p] = J.bits[p];
-      info[I_KF0 + p] = J.kf[p];
-      if (p >= 1 && p < J.npass && S + 1 > ((size_t)1 << TNS_SCAN_SMALL_LOG)) info[I_BIG_ROUTE] = 1;
-      if (p < J.npass) S <<= J.bits[p];
+      info[I_BITS0 + p] = sg.bits[p];
+      info[I_KF0 + p] = sg.kf[p];
+      // (a pass over S segments with S + 1 > SCAN_SMALL takes k_bs_tiles + exclusive_scan, not k_bs_geom)
+      if (p >= 1 && p < sg.npass && !sg.one_launch[p]) info[I_BIG_ROUTE] = 1;
     }
-    info[I_PK] = J.pk;
-    info[I_VO] = J.vo;
-    info[I_TILE] = J.npass > 1 ? J.tile : 0;
+    info[I_PK] = sg.pk;
+    info[I_VO] = sg.vo;
+    info[I_TILE] = sg.npass > 1 ? J.tile : 0;
     if (pending && J.readback) {  // the last pass's tile totals: all | those of multi-tile segments | entries
       const uint32_t *h = (const uint32_t *)J.readback;
       info[I_IDENT] = h[1] == 0;
@@ -126,9 +116,9 @@ int sortprobe_sort(tns_ctx *ctx, int form, const void *fr, const uint64_t *u64, 
     info[I_VALID0] = valid[0];
     info[I_VALID1] = valid[1];
     info[I_HAS_KEYS] = o.keys != nullptr;
-    info[I_KEYBITS] = J.keybits;
-    info[I_WB] = J.wb;
-    info[I_IBITS] = J.ibits;
+    info[I_KEYBITS] = sg.keybits;
+    info[I_WB] = sg.wb;
+    info[I_IBITS] = sg.ibits;
     info[I_COPIED] = (int64_t)take;
     TNS_HIP(hipDeviceSynchronize());  // (d_in is freed on return: nothing of the sort may still read it)
     TNS_LAUNCH_CHECK();
@@ -143,10 +133,10 @@ int sortprobe_hint(tns_ctx *ctx, int64_t out[5]) {
     CtxScope g(&ctx->c);
     const MsmLane::PlanHint &h = ctx->c.lanes[0].hint;
     out[0] = (int64_t)h.n;
-    out[1] = h.c;
-    out[2] = h.W;
-    out[3] = h.bucket_bits;
-    out[4] = h.shared ? 1 : 0;
+    out[1] = h.plan.c;
+    out[2] = h.plan.W;
+    out[3] = h.plan.bucket_bits;
+    out[4] = h.plan.shared ? 1 : 0;
     return TNS_OK;
   });
 }

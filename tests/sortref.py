@@ -16,7 +16,7 @@ import numpy as np
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 SIGN = 1 << 31
-# the compile-time pass-1 plans of bucket_sort.hip (kPass1Plans): (c, W) -> scalars per thread
+# the compile-time pass-1 shapes of msm_plan.hpp (kPass1Shapes): (c, W) -> scalars per thread
 CT_PLANS = {(22, 12): 3, (20, 13): 3, (19, 14): 3, (17, 15): 3, (16, 2): 16, (12, 2): 16}
 
 
@@ -71,7 +71,7 @@ def wb_of(W, shared):
 
 
 def bucket_bits_of(c, W, shared):
-    """what msm.hip's finish_plan hands the sort: wbits + c - 1 (shared: one bucket set)"""
+    """what msm_plan.hpp's finish_plan hands the sort: wbits + c - 1 (shared: one bucket set)"""
     wbits = 0
     if not shared:
         while (1 << wbits) < W:
@@ -100,6 +100,48 @@ def entries(limbs, c, W, shared, stride):
     out = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
     out.sort()
     return out
+
+
+# ---------------------------------------------------------------- the window planner
+# csrc/msm_plan.hpp's cost model restated (test_msm_plan_cpu.py compares the header with it,
+# test_gpu_msm_plan_grid.py the plans the device took).  The costs are integers below 2^53, so
+# the products with `tie` are the doubles the header computes.
+def windows_for(bits, c):
+    """signed c-bit windows of `bits`-bit scalars: the top window's raw value must stay <= 2^(c-1)"""
+    W = -(-bits // c)
+    return W + 1 if bits - c * (W - 1) > c - 1 else W
+
+
+def plan_cost(n, W, c, sets):
+    return W * n + 3 * sets * (1 << (c - 1))
+
+
+def best_window(n, bits, cmax, shared, w1max=0, tie=0.98):
+    lg, best, bc = (n - 1).bit_length(), 1e300, 4
+    for c in range(4, min(cmax, lg + 2) + 1):
+        W = windows_for(bits, c)
+        cost = plan_cost(n, W, c, 1 if shared else W)
+        if cost < best * tie:
+            best, bc = cost, c
+    c1 = bits + 1
+    return c1 if cmax < c1 <= min(w1max, lg + 2) and plan_cost(n, 1, c1, 1) < best * tie else bc
+
+
+def table_shape(n):
+    """(n, c, W) of the fixed-base window table over n points"""
+    c = best_window(n, 254, 22, True, 0, 1.0)
+    return n, c, windows_for(254, c)
+
+
+def plan_msm(n, bits, table=None, fb_off=0, tables=True):
+    """(c, W, bucket_bits, shared) of an MSM of n points by `bits`-bit scalars, and the stride"""
+    c = best_window(n, bits, 20, False, 23)
+    W, shared, stride = windows_for(bits, c), False, 0
+    if table and tables and table[0] >= fb_off + n and table[0] * table[2] < 1 << 31:
+        Ws = windows_for(bits, table[1])
+        if Ws <= table[2] and plan_cost(n, Ws, table[1], 1) < plan_cost(n, W, c, W):
+            c, W, shared, stride = table[1], Ws, True, table[0]
+    return (c, W, bucket_bits_of(c, W, shared), shared), stride
 
 
 # ---------------------------------------------------------------- the cases

@@ -19,6 +19,7 @@ import pytest
 
 from oracle import pyoracle as po
 
+import sortref
 import twist_and_shout as ts
 from twist_and_shout import _native as N
 
@@ -120,6 +121,10 @@ def run_size(n):
         limbs = scalars(n, width, seed=n * 1000 + width)
         for tables in (True, False):
             PLANS[(n, width, tables)] = msm_checked(limbs, tables, "n=%d, %d bits, tables %s" % (n, width, tables))
+            # the plan sortref's restatement of the cost model predicts: commits of >= 2^16 points come
+            # with the window table over the SRS's 2^18 + 1 points (kzg.hip srs_fixed_base)
+            table = sortref.table_shape((1 << 18) + 1) if tables and n >= 1 << 16 else None
+            assert PLANS[(n, width, tables)] == sortref.plan_msm(n, width, table)[0], (n, width, tables)
             checked += 1
     assert checked == 2 * len(WIDTHS + EXTRA_WIDTHS.get(n, []))
 
@@ -194,7 +199,7 @@ def test_single_window_plan_above_20_bits():
 
 
 def windows_for(bits, c):
-    """msm.hip's windows_for: the top window's raw value must stay <= 2^(c-1)"""
+    """msm_plan.hpp's windows_for: the top window's raw value must stay <= 2^(c-1)"""
     W = -(-bits // c)
     return W + 1 if bits - c * (W - 1) > c - 1 else W
 

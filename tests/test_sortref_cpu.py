@@ -11,7 +11,7 @@ ALL_PLANS = ref.PLANS + [ref.BIG_PLAN]
 
 
 def windows_for(bits, c):
-    """msm.hip's windows_for, from its comment: signed-digit windows of c bits for `bits`-bit
+    """msm_plan.hpp's windows_for, from its comment: signed-digit windows of c bits for `bits`-bit
     scalars -- the top window's raw value < 2^(bits - c (W-1)) must stay <= 2^(c-1) so that it
     never carries out."""
     W = -(-bits // c)
