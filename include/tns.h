@@ -274,6 +274,51 @@ int tns_commitment_hash(const uint64_t proj[12], uint64_t out[4]);
 /* Raw MSM: sum_i scalars[i] * points[i] over the first n SRS points. */
 int tns_msm(tns_ctx *ctx, const tns_srs *srs, const uint64_t *scalars, size_t n,
             uint64_t out_proj[12]);
+/* `batch` MSMs over the same n SRS points in one pass: KZGCommitment::commit's sum
+ * (src/commitments.rs:173-177) for every row of a row-major batch x n array of Montgomery scalars
+ * (row b = entries [b n, (b + 1) n)): out[b] = sum_i scalars[b n + i] * g1_powers[i].
+ * out_affine: batch points as affine uint64_t[8] each, identity = all zeros -- the encoding of
+ * tns_vc_open_all and tns_kzg_verify_many, so the rows go to the batched verifier unconverted.  Row b
+ * is the point tns_msm returns for that row.
+ * Route (csrc/msm_batch_plan.hpp, from the numbers alone): rows of fewer than 2^22 digit entries
+ * (windows x n for the batch's widest scalar: the measured crossover) are digitised,
+ * sorted, accumulated and reduced together -- one bit-length pass, then per group of rows one bucket
+ * sort, one accumulation, one reduction and a kernel for the window sums, and one finishing kernel a
+ * call (a fixed ~2 ms chain of doublings), with no host work or readback per row; longer rows (one
+ * MSM already fills the device) and batch == 1 run tns_msm's own route row by row on the one
+ * uploaded copy.  A batch whose digit entries (windows x rows x n
+ * < 2^31), keys (<= 31 bits) or workspace exceed what one sort allows is split into groups of rows
+ * run one after the other.
+ * Memory: a group's buffers -- about 28 bytes per digit entry, 320 bytes per bucket (rows x windows
+ * x 2^(c-1) buckets of 128 bytes with their reduction sums) and 40 bytes per key value -- live in
+ * the context's MSM workspaces and stay allocated at their high-water mark for the context's life,
+ * as a single MSM's do; groups are sized so that this stays below 1 GiB per context.  The uploaded
+ * rows (32 batch n bytes) and the results are call-scoped.
+ * Errors: a NULL context, SRS or required array -> TNS_ERR_INVALID_PARAMETERS; batch == 0 -> TNS_OK
+ * with no output; a sharded SRS, or batch * n above 2^32 scalars (or overflowing size_t) ->
+ * TNS_ERR_INVALID_PARAMETERS; n > srs_len -> TNS_ERR_COMMITMENT ("Polynomial degree exceeds setup
+ * size"); a failed device allocation -> TNS_ERR_OOM.  n == 0 returns identities.  Nothing is
+ * written on error. */
+int tns_msm_batch(tns_ctx *ctx, const tns_srs *srs, const uint64_t *scalars, size_t n, size_t batch,
+                  uint64_t *out_affine);
+/* tns_kzg_commit_evals (= KZGVectorCommitment::commit, src/commitments.rs:416-433) of every row of a
+ * batch x n array of evaluation vectors, as tns_msm_batch over the SRS's Lagrange basis of n nodes
+ * (the evaluations are the scalars).  When the SRS provides no such basis (no tau, nothing prepared
+ * or attached, or tns_ctx_set_commit_basis(0)) every row takes tns_kzg_commit_evals's interpolation
+ * route, with its results and its errors (n a power of two).  Output, memory and errors as
+ * tns_msm_batch; n == 0 -> TNS_ERR_POLYNOMIAL ("empty evaluation vector"). */
+int tns_kzg_commit_evals_batch(tns_ctx *ctx, const tns_srs *srs, const uint64_t *evals, size_t n, size_t batch,
+                               uint64_t *out_affine);
+/* tns_kzg_open_evals of every row at the same point z (src/commitments.rs:182-199 per row; with z an
+ * index as Fr this is KZGVectorCommitment::open(index) of every row, :435-471).  values_out: batch x
+ * uint64_t[4] (row b's interpolant at z); proofs_affine_out: batch affine points as above.  The
+ * inverses 1 / (z - j) are computed once for all rows; three kernels whose launch count does not
+ * depend on batch form the rows' values and quotient scalars (32 batch n bytes more, call-scoped),
+ * and one batched MSM over the Lagrange basis the proofs.  Without a Lagrange basis of n nodes every
+ * row takes tns_kzg_open_evals's own route, results and errors.  Errors otherwise as
+ * tns_kzg_commit_evals_batch (z, values_out and proofs_affine_out are required arrays). */
+int tns_kzg_open_evals_batch(tns_ctx *ctx, const tns_srs *srs, const uint64_t *evals, size_t n, size_t batch,
+                             const uint64_t z[4], uint64_t *values_out, uint64_t *proofs_affine_out);
 
 /* ---------------------------------------------------------------- polynomials */
 /* poly_utils::lagrange_interpolate over the nodes 0..n-1 (src/polynomials.rs:301-352,
@@ -354,6 +399,17 @@ int tns_vc_open_all_device(tns_ctx *ctx, tns_srs *srs, const uint64_t *d_vec, si
 /* KZGCommitment::commit / MSM on device-resident scalars. */
 int tns_msm_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_scalars, size_t n,
                    uint64_t out_proj[12]);
+/* tns_msm_batch, tns_kzg_commit_evals_batch and tns_kzg_open_evals_batch (the batched
+ * src/commitments.rs:173-177, :416-433 and :182-199) on rows already resident in HBM: d_scalars /
+ * d_evals is a device pointer to batch x n Montgomery Fr, only read; the outputs are host arrays
+ * (64 bytes a row, and 32 a value, are all that crosses PCIe).  Same results, memory and errors. */
+int tns_msm_batch_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_scalars, size_t n, size_t batch,
+                         uint64_t *out_affine);
+int tns_kzg_commit_evals_batch_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_evals, size_t n,
+                                      size_t batch, uint64_t *out_affine);
+int tns_kzg_open_evals_batch_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_evals, size_t n,
+                                    size_t batch, const uint64_t z[4], uint64_t *values_out,
+                                    uint64_t *proofs_affine_out);
 
 /* ---------------------------------------------------------------- verifiers (host)
  * CommitmentVerificationKey (src/utils.rs:64-75, :104-112): G1 generator, G2 generator and

@@ -107,6 +107,17 @@ void open_evals_pair(Ctx *c, const Srs &srs, EvalPoly &p0, EvalPoly &p1, const F
                      DevBuf &sbuf0, DevBuf &sbuf1, Comm &m, ExtraPayload *extra = nullptr,
                      const std::function<void()> &extra_ready = nullptr,
                      const std::function<void()> &side_work = nullptr);
+// kzg_batch.hip: `rows` vectors of n entries (rows x n Montgomery forms on the device) over one SRS,
+// results in host arrays of `rows` elements; lim: msm_batch_plan.hpp's limits (the entry points pass
+// the defaults, the probe of tests/device/batchprobe.hip forces routes and splits); rep (optional):
+// the route taken.  msm_batch_srs: out[b] = sum_i d_s[b n + i] g1_powers[i]; commit_evals_batch /
+// open_evals_batch: commit_evals / open_evals of every row (every row at the same z).
+void msm_batch_srs(Ctx *c, const Srs &srs, const Fr *d_s, size_t n, size_t rows, const BatchLimits &lim,
+                   G1Affine *out_host, BatchReport *rep);
+void commit_evals_batch(Ctx *c, const Srs &srs, const Fr *d_y, size_t n, size_t rows, const BatchLimits &lim,
+                        G1Affine *out_host, BatchReport *rep);
+void open_evals_batch(Ctx *c, const Srs &srs, const Fr *d_y, size_t n, size_t rows, const Fr &z, const BatchLimits &lim,
+                      Fr *values_host, G1Affine *proofs_host, BatchReport *rep);
 // abi_host.cpp: a tns_vk's three points, each checked against its curve
 struct Vk {
   G1Affine g1;

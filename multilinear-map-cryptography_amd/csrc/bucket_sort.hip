@@ -43,6 +43,9 @@ struct DigitArgs {
   bool mont;             // scalars are Montgomery forms: canonicalised here
   const uint64_t *u64;   // set: raw u64 scalars instead (entries [0, n_u64), zero above)
   size_t n_u64;
+  // a batch (WindowPlan::rows > 1; the ROWS kernels): scalar e = b n_row + i is row b's scalar of
+  // point i, and its window w belongs to bucket set b W + w
+  size_t n_row = 0;
 };
 
 // scalar i of the digit pass, canonical
@@ -61,10 +64,18 @@ __device__ __forceinline__ Fr load_scalar(const DigitArgs &A, size_t i) {
 // signed c-bit digits of scalar i (msm.hip k_digits): f(key, value) for every non-zero digit;
 // shared: key = (|d| - 1) << wb | w, value = (w * stride + i) | sign << 31
 // per-window: key = w << (c - 1) | (|d| - 1), value = i | sign << 31
-template <class F>
+// ROWS (a batch, per-window): scalar i is row b = i / n_row's scalar of point i % n_row:
+//   key = (b W + w) << (c - 1) | (|d| - 1), value = (i % n_row) | sign << 31
+template <bool ROWS = false, class F>
 __device__ __forceinline__ void scalar_digits(const Fr &s, size_t i, const DigitArgs &A, F f) {
   const Fr &k = s;  // canonical (load_scalar)
   uint32_t carry = 0;
+  uint32_t set0 = 0;  // the row's first bucket set
+  if (ROWS) {
+    const size_t b = i / A.n_row;
+    i -= b * A.n_row;
+    set0 = (uint32_t)b * (uint32_t)A.W;
+  }
   const int c = A.c;
   const uint32_t half = 1u << (c - 1);
   for (int w = 0; w < A.W; w++) {
@@ -88,6 +99,10 @@ __device__ __forceinline__ void scalar_digits(const Fr &s, size_t i, const Digit
       carry = 0;
     }
     if (mag) {
+      if (ROWS) {
+        f(((set0 + (uint32_t)w) << (c - 1)) | (mag - 1), (uint32_t)i | (neg << 31));
+        continue;
+      }
       const uint32_t key = A.shared ? ((mag - 1) << A.wb) | (uint32_t)w : ((uint32_t)w << (c - 1)) | (mag - 1);
       f(key, (uint32_t)(A.shared ? (size_t)w * A.stride + i : i) | (neg << 31));
     }
@@ -95,7 +110,7 @@ __device__ __forceinline__ void scalar_digits(const Fr &s, size_t i, const Digit
 }
 
 // each thread's scalars of a pass-1 tile, BS_SCALARS loads in flight at a time
-template <class F>
+template <bool ROWS = false, class F>
 __device__ __forceinline__ void tile_scalars(const DigitArgs &A, size_t a, size_t b, F f) {
   for (size_t i0 = a + threadIdx.x; i0 < b; i0 += (size_t)BS_SCALARS * BS_BLOCK) {
     Fr s[BS_SCALARS];
@@ -107,7 +122,7 @@ __device__ __forceinline__ void tile_scalars(const DigitArgs &A, size_t a, size_
 #pragma unroll
     for (int j = 0; j < BS_SCALARS; j++) {
       const size_t i = i0 + (size_t)j * BS_BLOCK;
-      if (i < b) scalar_digits(s[j], i, A, f);
+      if (i < b) scalar_digits<ROWS>(s[j], i, A, f);
     }
   }
 }
@@ -205,20 +220,22 @@ __device__ __forceinline__ void write_tile(const uint32_t *lk, const uint32_t *l
 }
 
 // pass 1 histogram: counts[d * T1 + tile] = entries of the tile with top digit d
+// (ROWS: a batch's tiles run over the rows x n_row scalars and may span row boundaries)
+template <bool ROWS>
 __global__ void __launch_bounds__(BS_BLOCK) k_bs_count1(DigitArgs A, int shift, int nbins, size_t T1,
                                                         uint32_t *__restrict__ counts) {
   __shared__ uint32_t h[BS_MAXBINS];
   for (int d = threadIdx.x; d < nbins; d += BS_BLOCK) h[d] = 0;
   __syncthreads();
   const size_t tile = blockIdx.x, a = tile * A.spb, b = min(A.n, a + A.spb);
-  tile_scalars(A, a, b, [&](uint32_t key, uint32_t) { atomicAdd(&h[key >> shift], 1u); });
+  tile_scalars<ROWS>(A, a, b, [&](uint32_t key, uint32_t) { atomicAdd(&h[key >> shift], 1u); });
   __syncthreads();
   for (int d = threadIdx.x; d < nbins; d += BS_BLOCK) counts[(size_t)d * T1 + tile] = h[d];
   if (tile == 0 && threadIdx.x == 0) counts[(size_t)nbins * T1] = 0;  // scan slot for the total
 }
 
 // pass 1 scatter: digits -> LDS ordered by bin -> coalesced runs
-template <int TILE>
+template <int TILE, bool ROWS>
 __global__ void __launch_bounds__(BS_BLOCK) k_bs_scatter1(DigitArgs A, int shift, int nbins, size_t T1,
                                                           const uint32_t *__restrict__ offs, int kf,
                                                           uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
@@ -230,12 +247,12 @@ __global__ void __launch_bounds__(BS_BLOCK) k_bs_scatter1(DigitArgs A, int shift
     goff[d] = offs[(size_t)d * T1 + tile];
   }
   __syncthreads();
-  tile_scalars(A, a, b, [&](uint32_t key, uint32_t) { atomicAdd(&h[key >> shift], 1u); });
+  tile_scalars<ROWS>(A, a, b, [&](uint32_t key, uint32_t) { atomicAdd(&h[key >> shift], 1u); });
   __syncthreads();
   block_scan_bins(h, lbase, nbins, wsum);
   for (int d = threadIdx.x; d < nbins; d += BS_BLOCK) h[d] = lbase[d];  // cursors
   __syncthreads();
-  tile_scalars(A, a, b, [&](uint32_t key, uint32_t val) {  // second digit sweep (scalars are cached)
+  tile_scalars<ROWS>(A, a, b, [&](uint32_t key, uint32_t val) {  // second digit sweep (scalars are cached)
     const uint32_t slot = atomicAdd(&h[key >> shift], 1u);
     lk[slot] = key;
     lv[slot] = val;
@@ -832,6 +849,9 @@ void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, const WindowP
                        BucketSortJob &J) {
   hipStream_t st = ln.stream;
   if ((size_t)plan.W * n >= ((size_t)1 << 32)) throw Error(TNS_ERR_COMMITMENT, "MSM too large for one bucket sort");
+  const bool rows = plan.rows > 1;  // a batch: n = rows x n_row scalars, the runtime pass-1 kernels alone
+  if (rows && (plan.shared || plan.n_row == 0 || (size_t)plan.rows * plan.n_row != n || in.precounted || in.low64))
+    throw Error(TNS_ERR_DEVICE, "batched bucket sort: per-window plans over rows x n_row scalars, nothing precounted");
   if (plan.W > BS_TILE) throw Error(TNS_ERR_COMMITMENT, "too many MSM windows");
   J = BucketSortJob();
   J.ln = &ln;
@@ -841,25 +861,28 @@ void bucket_sort_begin(MsmLane &ln, const SortInput &in, size_t n, const WindowP
   for (int k = 0; k < 2; k++) K[k] = (uint32_t *)ln.sort.keys[k].ensure(sizeof(uint32_t) * g.E);
   for (int k = 0; k < 2; k++) V[k] = (uint32_t *)ln.sort.vals[k].ensure(sizeof(uint32_t) * g.E);
   for (int k = 0; k < 2; k++) seg[k] = (uint32_t *)ln.sort.seg[k].ensure(sizeof(uint32_t) * (g.max_seg + 1));
-  const bool pre = in.precounted && g.ct >= 0 && same_counts(in.pre, plan) && ln.sort.counts.p == in.precounted &&
+  const bool pre = !rows && in.precounted && g.ct >= 0 && same_counts(in.pre, plan) && ln.sort.counts.p == in.precounted &&
                    ln.sort.counts.bytes >= sizeof(uint32_t) * g.cnt_len;
   uint32_t *counts = J.counts = (uint32_t *)ln.sort.counts.ensure(sizeof(uint32_t) * g.cnt_len);
   uint32_t *offs = J.offs = (uint32_t *)ln.sort.offs.ensure(sizeof(uint32_t) * g.cnt_len);
 
   // pass 1: scalars -> bins of the top bits[0] key bits (the compile-time kernels when there are
   // some for this window plan, else the runtime-plan kernels)
-  const DigitArgs A{in.fr, n, g.spb, plan.c, plan.W, g.wb, plan.shared, plan.stride, in.mont, in.u64, in.n_u64};
+  const DigitArgs A{in.fr, n, g.spb, plan.c, plan.W, g.wb, plan.shared, plan.stride, in.mont, in.u64, in.n_u64,
+                    rows ? plan.n_row : 0};
   const Pass1Kernels *ct = g.ct >= 0 ? &kPass1Kernels[g.ct] : nullptr;
   const unsigned T1 = (unsigned)g.T1;
   if (!pre) {  // (precounted: quotient2_count_dev or bucket_sort_precount_bits wrote them)
     if (ct) ct->count<<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, counts, nullptr, nullptr);
-    else k_bs_count1<<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, counts);
+    else if (rows) k_bs_count1<true><<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, counts);
+    else k_bs_count1<false><<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, counts);
     TNS_LAUNCH_CHECK();
   }
   exclusive_scan(st, ln.sort.scan, counts, offs, (size_t)g.nb * g.T1 + 1);
   const int kf1 = g.npass > 1 ? g.kf[0] : KF_U32;
   if (ct) ct->scatter<<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, offs, kf1, K[0], V[0]);
-  else k_bs_scatter1<BS_TILE><<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, offs, kf1, K[0], V[0]);
+  else if (rows) k_bs_scatter1<BS_TILE, true><<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, offs, kf1, K[0], V[0]);
+  else k_bs_scatter1<BS_TILE, false><<<T1, BS_BLOCK, 0, st>>>(A, g.shift, g.nb, g.T1, offs, kf1, K[0], V[0]);
   TNS_LAUNCH_CHECK();
   k_bs_segs1<<<1, 256, 0, st>>>(offs, g.nb, g.T1, seg[0], valid);
   TNS_LAUNCH_CHECK();

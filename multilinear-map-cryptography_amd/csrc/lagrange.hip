@@ -549,6 +549,37 @@ void lagrange_node_quotient_dev(Ctx *c, const Fr *y, size_t N, size_t j0, Fr *q)
   TNS_HIP(hipStreamSynchronize(c->stream));
 }
 
+// k_node_finish<false>'s backward sweep without a vector: out[i] = inv_i = 1 / (x - i), 0 at `skip`
+// (pre and out may alias)
+__global__ void __launch_bounds__(256) k_node_inverses(Fr x, size_t n, size_t T, Fr Tm, size_t skip, const Fr *pre,
+                                                       const Fr *__restrict__ cp, bool inverted, Fr *out) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (t >= T || t >= n) return;
+  size_t i = t + (n - 1 - t) / T * T;  // the chain's last element
+  Fr d = sub(x, from_u64<FrCfg>((uint64_t)i));
+  Fr iv = inverted ? cp[t] : inv(cp[t]);
+  for (;;) {
+    const bool hole = i == skip;
+    out[i] = hole ? Fr::zero() : mul(iv, pre[i]);
+    if (!hole) iv = mul(iv, d);
+    if (i < T) break;
+    i -= T;
+    d = add(d, Tm);
+  }
+}
+
+// The shared part of opening many vectors on the nodes 0..N-1 at one z (kzg_batch.hip): inv[j] =
+// 1 / (z - j) for every node (0 at j == skip: z is that node), and *ell_dev = prod (z - j) over the
+// nodes but `skip`, both on the device; queued on the context stream.
+void lagrange_inverses_dev(Ctx *c, size_t N, const Fr &z, size_t skip, Fr *inv, Fr *ell_dev) {
+  TNS_PROF(c, "open_scan", 32.0 * 3 * N);
+  NodeSweep s = node_sweep_begin(c, z, N, inv, skip);
+  k_node_inverses<<<grid_for(s.T, 256, 1u << 30), 256, 0, c->stream>>>(z, N, s.T, s.Tm, skip, inv, s.icp, s.inverted,
+                                                                      inv);
+  TNS_LAUNCH_CHECK();
+  TNS_HIP(hipMemcpyAsync(ell_dev, s.dev, sizeof(Fr), hipMemcpyDeviceToDevice, c->stream));
+}
+
 // Two vectors on the same nodes, opened at the same z (Twist: addresses and values): one
 // batch inversion serves both.  parts = {ell, sum0, sum1}; inv receives the shared inverses.
 // canon_inv: the inverses are written canonical (every chain inverse scaled by R^-1, the raw 1;

@@ -617,6 +617,10 @@ struct MsmJob {
   // a two-set tail), set res_set of res_sets
   MsmLane *res_lane = nullptr;
   int res_set = 0, res_sets = 1;
+  // a batch (msm_batch_groups_dev): the per-set sums stay on the device for k_batch_finish --
+  // msm_launch_tails publishes nothing and leaves them here (P.Wr x specs canonical points)
+  bool device_finish = false;
+  const G1Xyzz *sums = nullptr;
 };
 
 // ---------------------------------------------------------------- lane readbacks
@@ -993,7 +997,8 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     // k_accumulate, profiling)
     const void *src[3] = {out, J[0]->valid, nj == 2 ? J[1]->valid : nullptr};
     const size_t by[3] = {sizeof(G1Xyzz) * sets * specs, sizeof(uint32_t), sizeof(uint32_t)};
-    lane_publish(run, LANE_SLOT_SUMS, 1 + nj, src, by);
+    if (J[0]->device_finish) J[0]->sums = out;  // (thousands of sets: not through the lane's slot)
+    else lane_publish(run, LANE_SLOT_SUMS, 1 + nj, src, by);
   }
   for (int j = 0; j < nj; j++) {
     J[j]->L0 = L0;
@@ -1045,6 +1050,128 @@ G1Xyzz msm_dev(Ctx *ctx, const G1Affine *points, const Fr *scalars, size_t n, co
   MsmJob J;
   msm_queue_whole(ctx, ctx->lanes[0], MsmArgs{points, scalars, n, fb, fb_off}, J);
   return msm_complete(ctx, J);
+}
+
+// ---------------------------------------------------------------- a batch over one base
+// The finish of a batch on the device (msm_complete's host arithmetic), in two kernels:
+//  * k_batch_set_sums, per group: thread per bucket set forms window w of row b's sum
+//    R = sum_g T_g + L0 sum_s 2^s M_s from the set's specs (fin: sets x specs canonical points) into
+//    R[b W + w] -- a dozen dependent doublings and additions, every set in parallel;
+//  * k_batch_horner, ONCE for all groups: thread per row runs Horner over the row's W windows -- a
+//    chain of ~254 dependent doublings whatever the batch, so a fixed latency of the call (about
+//    2 ms) that no group repeats.  Only the rows' points leave the device.
+__global__ void __launch_bounds__(64) k_batch_set_sums(const G1Xyzz *__restrict__ fin, size_t sets, int specs, int nbits,
+                                                       int lgL0, G1Xyzz *__restrict__ R) {
+  const size_t set = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (set >= sets) return;
+  const G1Xyzz *f = fin + set * (size_t)specs;
+  G1Xyzz acc = G1Xyzz::inf();
+  for (int s = nbits - 1; s >= 0; s--) acc = xyzz_add(xyzz_dbl(acc), f[s]);
+  for (int k = 0; k < lgL0; k++) acc = xyzz_dbl(acc);
+  R[set] = xyzz_add(xyzz_add(f[nbits], f[nbits + 1]), acc);
+}
+
+__global__ void __launch_bounds__(64) k_batch_horner(const G1Xyzz *__restrict__ R, size_t rows, int W, int c,
+                                                     G1Xyzz *__restrict__ out) {
+  const size_t row = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const G1Xyzz *r = R + row * (size_t)W;
+  G1Xyzz acc = r[W - 1];
+  for (int j = W - 2; j >= 0; j--) {
+    for (int k = 0; k < c; k++) acc = xyzz_dbl(acc);
+    acc = xyzz_add(acc, r[j]);
+  }
+  out[row] = acc;
+}
+
+unsigned msm_batch_bits_dev(Ctx *ctx, const Fr *scalars, size_t total) {
+  if (!total) return 0;
+  MsmLane &ln = ctx->lanes[0];
+  unsigned *d_bits = (unsigned *)ln.msm.words.ensure(2 * sizeof(unsigned));
+  TNS_HIP(hipMemsetAsync(d_bits, 0, sizeof(unsigned), ln.stream));
+  {
+    TNS_PROF_ON(ctx, ln.stream, "msm_batch_bits", 32.0 * total);
+    k_scalar_bits<<<grid_for(total, 256, 2048), 256, 0, ln.stream>>>(scalars, total, d_bits, nullptr);
+    TNS_LAUNCH_CHECK();
+  }
+  const void *src[1] = {d_bits};
+  const size_t by[1] = {sizeof(unsigned)};
+  lane_publish(ln, LANE_SLOT_BITS, 1, src, by);
+  return bits_result(ln);
+}
+
+// One group after the other on lane 0: per group one sort (host wait: its last pass's tile totals),
+// one accumulation, one tail and the finish kernel -- no host work or readback per row.  The lane's
+// plan hint is left as the last single MSM wrote it.
+void msm_batch_groups_dev(Ctx *ctx, const G1Affine *points, const Fr *scalars, size_t n, size_t rows, unsigned bits,
+                          const BatchPlan &B, G1Affine *out, BatchReport *rep) {
+  if (B.route != BATCH_ROUTE_BATCHED || B.group_rows == 0 || bits == 0 || n == 0)
+    throw Error(TNS_ERR_DEVICE, "batched MSM without a batched plan");
+  MsmLane &ln = ctx->lanes[0];
+  hipStream_t st = ln.stream;
+  DevBuf rs, pre, wb;
+  G1Xyzz *rowsum = (G1Xyzz *)rs.ensure(sizeof(G1Xyzz) * rows);
+  const int W = B.P.W, c = B.P.c;  // (every group's: the window depends on n and the bits alone)
+  G1Xyzz *winsum = (G1Xyzz *)wb.ensure(sizeof(G1Xyzz) * rows * (size_t)W);  // R[b W + w]
+  Fq *prefix = (Fq *)pre.ensure(sizeof(Fq) * rows);
+  try {
+    for (size_t r0 = 0; r0 < rows; r0 += B.group_rows) {
+      const size_t g = std::min(B.group_rows, rows - r0);
+      // a group of zero rows among others has no digit entry to sort (a single MSM never sorts
+      // such scalars either: bits == 0 ends it): its window sums are identities
+      if (B.groups > 1 && msm_batch_bits_dev(ctx, scalars + r0 * n, g * n) == 0) {
+        TNS_HIP(hipMemsetAsync(winsum + r0 * (size_t)W, 0, sizeof(G1Xyzz) * g * (size_t)W, st));
+        continue;
+      }
+      MsmJob J;
+      J.lane = &ln;
+      J.ctx = ctx;
+      const MsmPlan &P = J.P = plan_batch_group(n, g, (int)bits);
+      if (P.W != W || P.c != c) throw Error(TNS_ERR_DEVICE, "batched MSM: a group with another window plan");
+      const size_t total = (size_t)P.W * g * n;
+      if (total >= ((size_t)1 << 31)) throw Error(TNS_ERR_COMMITMENT, "MSM batch group too large for one sort");
+      J.points = points;
+      J.n = g * n;
+      J.acc_k = acc_chunk(ctx, total, false);
+      J.nchunks = (total + J.acc_k - 1) / J.acc_k;
+      J.valid = (uint32_t *)ln.msm.words.ensure(2 * sizeof(uint32_t));
+      J.sort_prof.reset(new ProfScope(ctx->prof, st, "msm_sort", 32.0 * J.n + 16.0 * total));
+      SortInput in;
+      in.fr = scalars + r0 * n;
+      in.mont = true;
+      bucket_sort_begin(ln, in, g * n, P, J.valid, J.bs);
+      J.stage = MsmStage::Pass1Queued;
+      msm_sort_passes(J);
+      msm_finish_sort(J);
+      msm_launch_accumulate(ctx, J, nullptr);
+      J.device_finish = true;
+      MsmJob *one[1] = {&J};
+      msm_launch_tails(ctx, one, 1, ln);
+      int lgL0 = 0;
+      while ((1 << lgL0) < J.L0) lgL0++;
+      {
+        TNS_PROF_ON(ctx, st, "msm_batch_finish", 128.0 * P.Wr * J.specs);
+        k_batch_set_sums<<<grid_for((size_t)P.Wr, 64, 1u << 30), 64, 0, st>>>(J.sums, (size_t)P.Wr, J.specs, J.nbits, lgL0,
+                                                                              winsum + r0 * (size_t)W);
+        TNS_LAUNCH_CHECK();
+      }
+      if (rep) {
+        rep->c = P.c;
+        rep->W = P.W;
+        rep->npass = J.bs.g.npass;
+      }
+    }
+    {
+      TNS_PROF_ON(ctx, st, "msm_batch_finish", 128.0 * rows * W);
+      k_batch_horner<<<grid_for(rows, 64, 1u << 30), 64, 0, st>>>(winsum, rows, W, c, rowsum);
+      TNS_LAUNCH_CHECK();
+    }
+    xyzz_to_affine_batch_dev(ctx, rowsum, rows, out, prefix);
+    TNS_HIP(hipStreamSynchronize(st));  // the scratch dies here
+  } catch (...) {  // nothing queued here still runs on buffers that are then freed
+    (void)hipStreamSynchronize(st);
+    throw;
+  }
 }
 
 static void msm_pair_queue(Ctx *ctx, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]) {

@@ -14,6 +14,7 @@
 
 #include "bn254.hpp"
 #include "hip_util.hpp"
+#include "msm_batch_plan.hpp"
 #include "msm_plan.hpp"
 
 namespace tns {
@@ -204,6 +205,19 @@ struct MsmArgs {
 };
 // two independent MSMs overlapped on the context's two lanes (inputs ready on c->stream)
 void msm_pair_dev(Ctx *c, const MsmArgs &a, const MsmArgs &b, G1Xyzz out[2]);
+// A batch of `rows` MSMs over the same n points (msm_batch_plan.hpp), scalars rows x n Montgomery
+// forms on the device, all on lane 0 (= the context stream):
+//  * msm_batch_bits_dev: the largest bit length of all `total` scalars (one pass, one host wait);
+//  * msm_batch_groups_dev: the batched route of plan B (plan_batch with those bits) -- out[b], rows
+//    affine points on the device, = sum_i scalars[b n + i] points[i]; synchronises before it returns.
+// rep (optional): what the last group took.
+struct BatchReport {
+  int route = 0, c = 0, W = 0, npass = 0;
+  size_t groups = 0, group_rows = 0;
+};
+unsigned msm_batch_bits_dev(Ctx *c, const Fr *scalars, size_t total);
+void msm_batch_groups_dev(Ctx *c, const G1Affine *points, const Fr *scalars, size_t n, size_t rows, unsigned bits,
+                          const BatchPlan &B, G1Affine *out, BatchReport *rep = nullptr);
 std::unique_ptr<FixedBase> fixed_base_build_dev(Ctx *c, const G1Affine *points, size_t n);
 // the same, or nullptr when the table does not fit in device memory (TNS_ERR_OOM)
 std::unique_ptr<FixedBase> fixed_base_try_build(Ctx *c, const G1Affine *points, size_t n);

@@ -35,10 +35,16 @@ struct WindowPlan {
   bool shared = false;
   int bucket_bits = 0;
   uint32_t stride = 0;
+  // a batch of `rows` MSMs over the same n_row points sorted as one (per-window layout only): scalar
+  // e = b n_row + i of the rows x n_row array is row b's scalar of point i, and row b's window w is
+  // bucket set b W + w (msm_batch_plan.hpp).  rows == 1: one MSM, n_row unused.
+  uint32_t rows = 1;
+  size_t n_row = 0;
 };
 // pass-1 histograms counted for `a` serve a sort of the same scalars with `b` (the stride: values only)
 inline bool same_counts(const WindowPlan &a, const WindowPlan &b) {
-  return a.c == b.c && a.W == b.W && a.shared == b.shared && a.bucket_bits == b.bucket_bits;
+  return a.c == b.c && a.W == b.W && a.shared == b.shared && a.bucket_bits == b.bucket_bits && a.rows == b.rows &&
+         (a.rows == 1 || a.n_row == b.n_row);
 }
 // the plan with what the reduction needs
 struct MsmPlan : WindowPlan {
@@ -130,7 +136,8 @@ struct Pass1Shape { int c, W, spt; };
 constexpr Pass1Shape kPass1Shapes[] = {{22, 12, 3}, {20, 13, 3}, {19, 14, 3}, {17, 15, 3}, {16, 2, 16}, {12, 2, 16}};
 constexpr int kPass1ShapeCount = (int)(sizeof(kPass1Shapes) / sizeof(kPass1Shapes[0]));
 
-// Everything a sort of the W n digit entries of n scalars derives from numbers alone.
+// Everything a sort of the W n digit entries of n scalars derives from numbers alone (a batch,
+// plan.rows > 1: n = rows x n_row scalars in all).
 struct SortGeom {
   size_t E = 0;  // entry slots (W n)
   WindowPlan plan;
@@ -175,8 +182,8 @@ inline SortGeom sort_geom(size_t n, const WindowPlan &plan) {
   // 9, 9, 7, measured slower: it moved the cost into 512-bin passes, +3.3 ms of sort per C4 step
   // against -0.8 ms of reads.)  Values-only last pass (vo): whenever there is more than one pass --
   // the accumulation reads no keys (C4: k_accumulate 9.10 -> 8.8 ms).
-  g.ibits = 1;
-  while (((size_t)1 << g.ibits) < n) g.ibits++;
+  g.ibits = 1;  // (a batch's values are point indices of one row)
+  while (((size_t)1 << g.ibits) < (plan.rows > 1 ? plan.n_row : n)) g.ibits++;
   g.vo = npass >= 2;
   // (unpack_value reads the window index from the low wb bits of the last pass's L key bits: L >= wb)
   g.pk = g.vo && npass >= 3 && last + g.ibits + 1 <= 32 && last >= g.wb;
@@ -191,7 +198,7 @@ inline SortGeom sort_geom(size_t n, const WindowPlan &plan) {
   // pass 1: scalars -> bins of the top bits[0] key bits
   g.nb = 1 << bits[0];
   g.shift = keybits - bits[0];
-  for (int k = 0; k < kPass1ShapeCount; k++)
+  for (int k = 0; k < kPass1ShapeCount && plan.rows == 1; k++)  // (a batch: the runtime kernels)
     if (kPass1Shapes[k].c == plan.c && kPass1Shapes[k].W == plan.W) g.ct = k;
   g.spb = (size_t)BS_TILE / plan.W;
   if (g.ct >= 0) g.spb = std::min(g.spb, (size_t)BS_BLOCK * kPass1Shapes[g.ct].spt);

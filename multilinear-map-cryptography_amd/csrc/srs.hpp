@@ -70,6 +70,9 @@ void lagrange_quotient_finish2_dev(Ctx *c, const Fr *y0, const Fr *y1, size_t cn
 // quotient values for an opening AT the node j0 (value y_j0), unsharded
 void lagrange_node_quotient_dev(Ctx *c, const Fr *y, size_t N, size_t j0, Fr *q);
 bool fr_is_node(const Fr &x, size_t N);
+// the shared inverses of opening many vectors at one z: inv[j] = 1 / (z - j), j < N (0 at j == skip, the
+// node z is; SIZE_MAX: none), *ell_dev = prod over the other nodes of (z - j); device outputs, queued
+void lagrange_inverses_dev(Ctx *c, size_t N, const Fr &z, size_t skip, Fr *inv, Fr *ell_dev);
 // barycentric weights w_j = (-1)^(N-1-j) / (j! (N-1-j)!) of the nodes [first, first + cnt) (cached)
 const Fr *bary_weights_dev(Ctx *c, size_t N, size_t first, size_t cnt);
 // tfree.hip: the Lagrange basis [L_j(tau)]G, j < N, from g1_powers[0..N) alone (no tau); cached in

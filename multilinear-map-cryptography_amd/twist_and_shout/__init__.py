@@ -580,6 +580,41 @@ def _affine_limbs(pts: Sequence[G1Affine]) -> np.ndarray:
     return out
 
 
+def _points_from_limbs(limbs: np.ndarray) -> List[G1Affine]:
+    """(n, 8) affine Montgomery limbs, identity = zeros -> [None | (x, y)] (the inverse of _affine_limbs)."""
+    a = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 8)
+    live = [i for i in range(len(a)) if a[i].any()]
+    out: List[G1Affine] = [None] * len(a)
+    if live:
+        xs, ys = from_mont(a[live, :4], P_MOD), from_mont(a[live, 4:], P_MOD)
+        for k, i in enumerate(live):
+            out[i] = (xs[k], ys[k])
+    return out
+
+
+def _rows_mont(rows) -> Tuple[np.ndarray, int, int]:
+    """A batch of equally long vectors -> ((B * n, 4) Montgomery limbs, B, n): a (B, n, 4) uint64
+    array as it is, else a sequence of B integer sequences."""
+    if isinstance(rows, np.ndarray) and rows.dtype == np.uint64 and rows.ndim == 3:
+        b, n = rows.shape[0], rows.shape[1]
+        return np.ascontiguousarray(rows).reshape(-1, 4), b, n
+    rows = [list(r) for r in rows]
+    b = len(rows)
+    n = len(rows[0]) if b else 0
+    if any(len(r) != n for r in rows):
+        raise InvalidParameters("the rows of a batch must have one length")
+    flat = [x for r in rows for x in r]
+    return (to_mont(flat) if flat else np.zeros((0, 4), dtype=np.uint64)), b, n
+
+
+def _batch_points(call, b: int, raw: bool, wrap):
+    """Run call(out) of one of the batched MSM entry points: the (B, 8) limb array, or wrap(point) per row."""
+    out = np.zeros((max(b, 1), 8), dtype=np.uint64)
+    _check(call(N.p64(out)))
+    out = out[:b]
+    return out if raw else [wrap(p) for p in _points_from_limbs(out)]
+
+
 def _proof_limbs(proofs) -> np.ndarray:
     """An (n, 8) array as open_all returns it, or a list of KZGProof -> the (n, 8) array."""
     if isinstance(proofs, np.ndarray):
@@ -702,6 +737,29 @@ class KZGCommitment:
         return from_mont(v)[0], KZGProof(_g1_from_proj(pi))
 
 
+    @staticmethod
+    def commit_evaluations_batch(params: CommitmentParams, rows, raw: bool = False):
+        """commit_evaluations of every row of a batch of equally long vectors in one batched MSM
+        (tns_kzg_commit_evals_batch): a list of KZGCommitmentValue, or with raw=True the (B, 8) array
+        of affine Montgomery limbs (identity = zeros) that verify_many takes."""
+        y, b, n = _rows_mont(rows)
+        srs = params.srs
+        return _batch_points(lambda out: N.load().tns_kzg_commit_evals_batch(
+            srs.ctx.handle, srs.handle, N.p64(_nonempty(y)), n, b, out), b, raw, KZGCommitmentValue)
+
+    @staticmethod
+    def open_evaluations_batch(params: CommitmentParams, rows, point: int, raw: bool = False):
+        """open_evaluations(params, row, point) of every row at the one point (tns_kzg_open_evals_batch):
+        (values, proofs) -- a list of ints and a list of KZGProof, or with raw=True the (B, 8) array."""
+        y, b, n = _rows_mont(rows)
+        srs = params.srs
+        v = np.zeros((max(b, 1), 4), dtype=np.uint64)
+        z = to_mont([point])[0]
+        pis = _batch_points(lambda out: N.load().tns_kzg_open_evals_batch(
+            srs.ctx.handle, srs.handle, N.p64(_nonempty(y)), n, b, N.p64(z), N.p64(v), out), b, raw, KZGProof)
+        return from_mont(v[:b]), pis
+
+
 class KZGVectorCommitment:
     """``impl VectorCommitmentScheme for KZGVectorCommitment`` (src/commitments.rs:408-483):
     KZG over the interpolant of the vector on the nodes 0..n-1."""
@@ -718,6 +776,20 @@ class KZGVectorCommitment:
         _check(N.load().tns_vc_open(params.srs.ctx.handle, params.srs.handle, N.p64(_nonempty(y)), len(y), index,
                                     N.p64(v), N.p64(pi)))
         return from_mont(v)[0], KZGProof(_g1_from_proj(pi))
+
+    @staticmethod
+    def commit_batch(params: CommitmentParams, vectors, raw: bool = False):
+        """commit(params, v) of every vector of a batch of equally long vectors (one batched MSM)."""
+        return KZGCommitment.commit_evaluations_batch(params, vectors, raw)
+
+    @staticmethod
+    def open_batch(params: CommitmentParams, vectors, index: int, raw: bool = False):
+        """open(params, v, index) of every vector at the one index: (values, proofs) as
+        KZGCommitment.open_evaluations_batch returns them."""
+        n = len(vectors[0]) if len(vectors) else 0
+        if len(vectors) and not 0 <= index < n:
+            raise CommitmentError("Index out of bounds")
+        return KZGCommitment.open_evaluations_batch(params, vectors, index, raw)
 
     @staticmethod
     def open_all(params: CommitmentParams, vector) -> np.ndarray:
@@ -773,6 +845,15 @@ def msm(params: CommitmentParams, scalars) -> G1Affine:
     out = np.zeros(12, dtype=np.uint64)
     _check(N.load().tns_msm(params.srs.ctx.handle, params.srs.handle, N.p64(_nonempty(c)), len(c), N.p64(out)))
     return _g1_from_proj(out)
+
+
+def msm_batch(params: CommitmentParams, rows, raw: bool = False):
+    """msm(params, row) of every row of a batch of equally long scalar vectors in one batched pass
+    (tns_msm_batch): a list of points, or with raw=True the (B, 8) array of affine Montgomery limbs."""
+    c, b, n = _rows_mont(rows)
+    srs = params.srs
+    return _batch_points(lambda out: N.load().tns_msm_batch(srs.ctx.handle, srs.handle, N.p64(_nonempty(c)), n, b, out),
+                         b, raw, lambda p: p)
 
 
 # ----------------------------------------------------------------------------- polynomials
@@ -1396,6 +1477,30 @@ def msm_resident(params: CommitmentParams, scalars: DeviceBuffer, n: int) -> np.
     return out
 
 
+def msm_batch_resident(params: CommitmentParams, scalars: DeviceBuffer, n: int, batch: int) -> np.ndarray:
+    """msm_batch on rows resident in HBM (batch x n Fr, Montgomery, row-major): the (batch, 8) limb array."""
+    srs = params.srs
+    return _batch_points(lambda out: N.load().tns_msm_batch_device(srs.ctx.handle, srs.handle, scalars.ptr, n, batch,
+                                                                   out), batch, True, None)
+
+
+def commit_evaluations_batch_resident(params: CommitmentParams, rows: DeviceBuffer, n: int, batch: int) -> np.ndarray:
+    """KZGCommitment.commit_evaluations_batch on resident rows: the (batch, 8) limb array."""
+    srs = params.srs
+    return _batch_points(lambda out: N.load().tns_kzg_commit_evals_batch_device(srs.ctx.handle, srs.handle, rows.ptr, n,
+                                                                                batch, out), batch, True, None)
+
+
+def open_evaluations_batch_resident(params: CommitmentParams, rows: DeviceBuffer, n: int, batch: int, point: int):
+    """KZGCommitment.open_evaluations_batch on resident rows: (values as ints, the (batch, 8) limb array)."""
+    srs = params.srs
+    v = np.zeros((max(batch, 1), 4), dtype=np.uint64)
+    z = to_mont([point])[0]
+    pis = _batch_points(lambda out: N.load().tns_kzg_open_evals_batch_device(
+        srs.ctx.handle, srs.handle, rows.ptr, n, batch, N.p64(z), N.p64(v), out), batch, True, None)
+    return from_mont(v[:batch]), pis
+
+
 def vc_open_all_resident(params: CommitmentParams, vector: DeviceBuffer, n: int, proofs: DeviceBuffer):
     """KZGVectorCommitment.open_all on a vector resident in HBM (n Fr, Montgomery) into a resident
     output of n affine points (64 n bytes; buffer_download reads it): tns_vc_open_all_device."""
@@ -1767,5 +1872,5 @@ __all__ = [
     "MemoryOp", "MemoryTrace", "Twist", "TwistProof", "LookupOp", "LookupTable", "Shout", "ShoutProof",
     "bench_trace", "to_mont", "from_mont", "fr_from_u64_array", "device_count", "Comm", "setup_params_shard",
     "shard_slice", "bench_trace_slice", "KZGVectorCommitment", "CommitmentVerificationKey", "pairing",
-    "g1_serialize", "g1_deserialize", "verify_challenges",
+    "g1_serialize", "g1_deserialize", "verify_challenges", "msm_batch",
 ]

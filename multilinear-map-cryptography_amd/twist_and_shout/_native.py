@@ -113,6 +113,9 @@ SIGNATURES = [
     ("tns_vc_open_all_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("tns_commitment_hash", C.c_int, [U64P, U64P]),
     ("tns_msm", C.c_int, [C.c_void_p, C.c_void_p, U64P, C.c_size_t, U64P]),
+    ("tns_msm_batch", C.c_int, [C.c_void_p, C.c_void_p, U64P, C.c_size_t, C.c_size_t, U64P]),
+    ("tns_kzg_commit_evals_batch", C.c_int, [C.c_void_p, C.c_void_p, U64P, C.c_size_t, C.c_size_t, U64P]),
+    ("tns_kzg_open_evals_batch", C.c_int, [C.c_void_p, C.c_void_p, U64P, C.c_size_t, C.c_size_t, U64P, U64P, U64P]),
     ("tns_interpolate_consecutive", C.c_int, [C.c_void_p, U64P, C.c_size_t, U64P]),
     ("tns_mle_evaluate", C.c_int, [C.c_void_p, U64P, C.c_size_t, C.c_uint, U64P, U64P]),
     ("tns_mle_partial_evaluate", C.c_int, [C.c_void_p, U64P, C.c_size_t, C.c_uint, U64P, C.c_uint, U64P]),
@@ -144,6 +147,10 @@ SIGNATURES = [
      [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
       C.POINTER(TnsProof)]),
     ("tns_msm_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, U64P]),
+    ("tns_msm_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P]),
+    ("tns_kzg_commit_evals_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P]),
+    ("tns_kzg_open_evals_batch_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P, U64P, U64P]),
     ("tns_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("tns_profile_only", C.c_int, [C.c_void_p, C.c_char_p]),
     ("tns_profile_read_ex", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
