@@ -126,7 +126,7 @@ struct Ctx {
   DevBuf qbits;        // opening quotients' bit lengths (lagrange_quotient_finish2_dev)
   MsmLane lanes[2];     // lanes[0].stream == stream; lanes[1] has its own stream
   ProveWs prove;
-  DevBuf twiddles;  // omega_{2^k}^i, i < 2^(k-1), natural order, for the largest k seen
+  DevBuf twiddles;  // stage-major TW[h + k] = w_{2h}^k (ntt.hpp), 2^twiddle_log entries, for the largest size seen
   unsigned twiddle_log = 0;
   DevBuf glv_tw;    // the same table split for the group NTT (glv_twiddles), for the largest k vc_open.hip saw
   unsigned glv_tw_log = 0;

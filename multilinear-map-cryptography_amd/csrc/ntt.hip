@@ -7,8 +7,8 @@
 //     LDS before writing back -- one HBM read and write per r stages instead of per stage;
 //   * a contiguous 1024-element LDS tile for the 10 smallest strides.
 // ntt_conv_blocks fuses the last forward tile pass, the pointwise product and the
-// first inverse tile pass into one kernel, so a size-2^24 cyclic convolution is
-// 2 + 1 + 2 = 5 passes over HBM.
+// first inverse tile pass into one kernel, so a size-2^24 cyclic convolution (14 strided
+// stages, three passes each way) is 3 + 1 + 3 = 7 passes over HBM.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

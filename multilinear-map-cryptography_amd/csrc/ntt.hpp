@@ -122,7 +122,7 @@ const Fr *ntt_twiddles(Ctx *c, unsigned L);  // ensure stages < L; returns TW
 // nb contiguous transforms of size 2^s (forward DIF or inverse DIT, unscaled)
 void ntt_blocks(Ctx *c, Fr *x, unsigned s, size_t nb, bool inverse);
 // x <- INTT(NTT(x) .* w) per block (w: a forward transform of size 2^s in bit-reversed
-// order, pre-scaled by 2^-s): a cyclic convolution in 2 + 2*ceil((s-10)/7) HBM passes.
+// order, pre-scaled by 2^-s): a cyclic convolution in 1 + 2*ceil((s-10)/5) HBM passes.
 void ntt_conv_blocks(Ctx *c, Fr *x, unsigned s, size_t nb, const Fr *w);
 Fr fr_root_of_unity(unsigned log_order);
 

@@ -284,12 +284,60 @@ def test_interpolate_large_roundtrip(logn):
         assert co.fr_ints(co.horner(coeffs, co.fr_array([z])[0]))[0] == po.barycentric_eval(ys, z)
 
 
+def reproduces_every_node(coeffs, y):
+    """Evaluates the n coefficients at every node 0..n-1 (oracle Horner) against y, limb for limb:
+    n coefficients that reproduce all n values are the interpolant.  Returns the nodes compared."""
+    n = len(y)
+    assert coeffs.shape == (n, 4)
+    nodes = co.fr_array(range(n))
+    checked = 0
+    for i in range(n):
+        assert np.array_equal(co.horner(coeffs, nodes[i]), y[i]), "node %d of %d" % (i, n)
+        checked += 1
+    return checked
+
+
+@pytest.mark.parametrize("logn", [10, 11, 12])
+def test_interpolate_all_nodes(logn):
+    """Above the fused 512-element tile, exact at every node.  2^10: the first global level
+    (l = 9, one block); 2^11: a global level of two blocks, and a strided pass inside
+    ntt_conv_blocks; 2^12: three global levels of 4, 2 and 1 blocks."""
+    n = 1 << logn
+    y = rand_fr_mont(n, seed=2000 + logn)
+    coeffs = ts.poly_utils.interpolate_consecutive(y)
+    assert reproduces_every_node(coeffs, y) == n
+
+
 def test_interpolate_structured_inputs():
     for logn in (4, 8):
         n = 1 << logn
         for vals in ([0] * n, [1] * n, list(range(n)), [i * i for i in range(n)], [R - 1] * n):
             y = ts.to_mont(vals)
             assert np.array_equal(ts.poly_utils.interpolate_consecutive(y), co.interpolate(y))
+    # above the fused tile, against closed forms (no oracle interpolation): the monomials 0, 1, x,
+    # x^2 and x^(n-1), and the last Lagrange basis polynomial, whose leading coefficient is
+    # 1 / prod_{j < n-1} (n - 1 - j) = 1 / (n-1)!
+    checked = 0
+    for logn in (10, 11):
+        n = 1 << logn
+
+        def unit(k, n=n):
+            return ts.to_mont([1 if i == k else 0 for i in range(n)])
+
+        cases = [([0] * n, ts.to_mont([0] * n)), ([1] * n, unit(0)), (list(range(n)), unit(1)),
+                 ([i * i for i in range(n)], unit(2)), ([pow(i, n - 1, R) for i in range(n)], unit(n - 1))]
+        for vals, want in cases:
+            assert np.array_equal(ts.poly_utils.interpolate_consecutive(ts.to_mont(vals)), want), (logn, vals[:4])
+            checked += 1
+        y = unit(n - 1)
+        coeffs = ts.poly_utils.interpolate_consecutive(y)
+        fact = 1
+        for k in range(1, n):
+            fact = fact * k % R
+        assert np.array_equal(coeffs[n - 1], ts.to_mont([pow(fact, -1, R)])[0]), logn
+        assert reproduces_every_node(coeffs, y) == n
+        checked += 1
+    assert checked == 12
 
 
 # ---------------------------------------------------------------- MLE
