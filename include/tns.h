@@ -319,6 +319,16 @@ int tns_kzg_commit_evals_batch(tns_ctx *ctx, const tns_srs *srs, const uint64_t 
  * tns_kzg_commit_evals_batch (z, values_out and proofs_affine_out are required arrays). */
 int tns_kzg_open_evals_batch(tns_ctx *ctx, const tns_srs *srs, const uint64_t *evals, size_t n, size_t batch,
                              const uint64_t z[4], uint64_t *values_out, uint64_t *proofs_affine_out);
+/* tns_kzg_open_evals of row b at its own point points[b] (src/commitments.rs:182-199 per row; with
+ * points[b] an index i_b as Fr this is KZGVectorCommitment::open(i_b) of vector b, :435-471).  points:
+ * batch x uint64_t[4], Montgomery, on the host.  Nodes and other points may be mixed in one call, and
+ * rows may share a point.  All batch * n inverses 1 / (points[b] - j) come from one batch inversion
+ * (one modular inverse per 1024 of them), and the launch count depends neither on batch nor on the
+ * points: about 64 batch n bytes of inverses and coefficients and 32 batch n of quotient scalars,
+ * call-scoped.  Everything else -- route, fallback, outputs, checks and their order, batch == 0 -- as
+ * tns_kzg_open_evals_batch. */
+int tns_kzg_open_evals_batch_points(tns_ctx *ctx, const tns_srs *srs, const uint64_t *evals, size_t n, size_t batch,
+                                    const uint64_t *points, uint64_t *values_out, uint64_t *proofs_affine_out);
 
 /* ---------------------------------------------------------------- polynomials */
 /* poly_utils::lagrange_interpolate over the nodes 0..n-1 (src/polynomials.rs:301-352,
@@ -375,6 +385,36 @@ int tns_twist_prove(tns_ctx *ctx, const tns_srs *srs, const tns_params *params,
 int tns_shout_prove(tns_ctx *ctx, const tns_srs *srs, const tns_params *params,
                     const uint64_t *entries, size_t n_entries, const uint64_t *indices,
                     size_t n_lookups, tns_proof *out);
+/* Twist::prove (src/twist.rs:107-252) of `batch` independent traces of n_ops operations each, over one
+ * SRS in one call.  Row-major inputs: addr batch x n_ops, value batch x n_ops x 4,
+ * is_write batch x n_ops bytes; out: batch proofs.  out[b] is byte for byte what tns_twist_prove
+ * returns for row b alone, the diagnostics included.
+ * Route (csrc/prove_batch_plan.hpp): with N = next_pow2(n_ops), the batched route is taken when
+ * batch >= 2, N >= 2, the SRS provides the Lagrange basis of N nodes, and the full-width rows take
+ * tns_msm_batch's batched route (rows below its crossover).  Then every stage runs once for all
+ * proofs: one kernel for the padded address tables, two batched commitments (addresses, values), one
+ * host transcript a proof, one fold launch a round over all proofs and tables, and one batched
+ * opening of the 2 batch rows with a point per proof.  Otherwise tns_twist_prove runs row by row.
+ * Memory: the batched route holds about 32 bytes x batch x N x 10.25 call-scoped (the address and
+ * padded value tables, 2.25 tables of fold scratch, the 2 interleaved opening rows, their 2 quotient
+ * rows and 2 rows of inverses and coefficients) beside tns_msm_batch's workspaces.
+ * Errors: a NULL handle or required array, a sharded SRS, batch * N above 2^32 ->
+ * TNS_ERR_INVALID_PARAMETERS; n_ops > max_operations -> TNS_ERR_INVALID_PARAMETERS ("Too many
+ * operations"); a failed device allocation -> TNS_ERR_OOM.  batch == 0 -> TNS_OK, nothing written.
+ * On error nothing the call queued is still running and `out` is unspecified.
+ * tns_last_prove_timing reports the whole call in slot 5; on the batched route also the two batched
+ * commitments in slot 2, the host transcripts in slot 3 and the folds and openings in slot 4. */
+int tns_twist_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *addr,
+                          const uint64_t *value, const uint8_t *is_write, size_t n_ops, size_t batch, tns_proof *out);
+/* Shout::prove (src/shout.rs:97-222) of `batch` independent (table, lookups) pairs of one shape:
+ * entries batch x n_entries x 4, indices batch x n_lookups.  As tns_twist_prove_batch with
+ * T = next_pow2(n_entries) table nodes and M = next_pow2(n_lookups) index nodes (batched when M >= 2
+ * and both bases exist); the table rows and the index rows are committed in a call each, and opened
+ * in one call when T == M, else in a call each.  An index >= n_entries in any row fails the whole
+ * call with TNS_ERR_INVALID_PARAMETERS ("Lookup index out of bounds"); n_lookups > max_operations ->
+ * "Too many lookup operations". */
+int tns_shout_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *entries,
+                          size_t n_entries, const uint64_t *indices, size_t n_lookups, size_t batch, tns_proof *out);
 
 /* ---------------------------------------------------------------- device-resident inputs */
 /* The same provers on inputs already resident in HBM (device pointers, e.g. from
@@ -410,6 +450,19 @@ int tns_kzg_commit_evals_batch_device(tns_ctx *ctx, const tns_srs *srs, const ui
 int tns_kzg_open_evals_batch_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_evals, size_t n,
                                     size_t batch, const uint64_t z[4], uint64_t *values_out,
                                     uint64_t *proofs_affine_out);
+/* tns_kzg_open_evals_batch_points (src/commitments.rs:182-199 per row) on resident rows; points stay
+ * a host array. */
+int tns_kzg_open_evals_batch_points_device(tns_ctx *ctx, const tns_srs *srs, const uint64_t *d_evals, size_t n,
+                                           size_t batch, const uint64_t *points, uint64_t *values_out,
+                                           uint64_t *proofs_affine_out);
+/* tns_twist_prove_batch (src/twist.rs:107-252) and tns_shout_prove_batch (src/shout.rs:97-222) on
+ * inputs resident in HBM, row-major as above and only read; out is a host array. */
+int tns_twist_prove_batch_device(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *d_addr,
+                                 const uint64_t *d_value, const uint8_t *d_is_write, size_t n_ops, size_t batch,
+                                 tns_proof *out);
+int tns_shout_prove_batch_device(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *d_entries,
+                                 size_t n_entries, const uint64_t *d_indices, size_t n_lookups, size_t batch,
+                                 tns_proof *out);
 
 /* ---------------------------------------------------------------- verifiers (host)
  * CommitmentVerificationKey (src/utils.rs:64-75, :104-112): G1 generator, G2 generator and

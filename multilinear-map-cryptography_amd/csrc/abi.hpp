@@ -118,6 +118,24 @@ void commit_evals_batch(Ctx *c, const Srs &srs, const Fr *d_y, size_t n, size_t 
                         G1Affine *out_host, BatchReport *rep);
 void open_evals_batch(Ctx *c, const Srs &srs, const Fr *d_y, size_t n, size_t rows, const Fr &z, const BatchLimits &lim,
                       Fr *values_host, G1Affine *proofs_host, BatchReport *rep);
+// open_evals_batch with one point per g consecutive rows (row r at points_host[r / g], ceil(rows / g)
+// Montgomery points on the host; nodes and other points may be mixed): the public calls pass g = 1,
+// the batched provers g = 2 so that a proof's two vectors share their inverses
+void open_evals_batch_points(Ctx *c, const Srs &srs, const Fr *d_y, size_t n, size_t rows, const Fr *points_host,
+                             size_t g, const BatchLimits &lim, Fr *values_host, G1Affine *proofs_host,
+                             BatchReport *rep);
+// prove_batch.hip: what the batched provers' stages took (tests/device/provebatchprobe.hip)
+struct ProveBatchReport {
+  int route = 0;
+  BatchReport commit[2], open[2];  // commitments 0 and 1; opening calls (one call: open[0] alone)
+  int open_calls = 0, rows_per_point = 0;
+};
+int twist_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *addr,
+                      const uint64_t *value, const uint8_t *is_write, size_t n_ops, size_t batch, tns_proof *out,
+                      bool resident, const BatchLimits &lim, ProveBatchReport *rep);
+int shout_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *entries,
+                      size_t n_entries, const uint64_t *indices, size_t n_lookups, size_t batch, tns_proof *out,
+                      bool resident, const BatchLimits &lim, ProveBatchReport *rep);
 // abi_host.cpp: a tns_vk's three points, each checked against its curve
 struct Vk {
   G1Affine g1;

@@ -759,6 +759,21 @@ class KZGCommitment:
             srs.ctx.handle, srs.handle, N.p64(_nonempty(y)), n, b, N.p64(z), N.p64(v), out), b, raw, KZGProof)
         return from_mont(v[:b]), pis
 
+    @staticmethod
+    def open_evaluations_batch_points(params: CommitmentParams, rows, points, raw: bool = False):
+        """open_evaluations(params, rows[b], points[b]) for every row at its own point
+        (tns_kzg_open_evals_batch_points): (values, proofs) as open_evaluations_batch returns them."""
+        y, b, n = _rows_mont(rows)
+        points = [int(p) for p in points]
+        if len(points) != b:
+            raise InvalidParameters("one opening point per row")
+        srs = params.srs
+        v = np.zeros((max(b, 1), 4), dtype=np.uint64)
+        z = to_mont(points) if b else np.zeros((1, 4), dtype=np.uint64)
+        pis = _batch_points(lambda out: N.load().tns_kzg_open_evals_batch_points(
+            srs.ctx.handle, srs.handle, N.p64(_nonempty(y)), n, b, N.p64(z), N.p64(v), out), b, raw, KZGProof)
+        return from_mont(v[:b]), pis
+
 
 class KZGVectorCommitment:
     """``impl VectorCommitmentScheme for KZGVectorCommitment`` (src/commitments.rs:408-483):
@@ -790,6 +805,18 @@ class KZGVectorCommitment:
         if len(vectors) and not 0 <= index < n:
             raise CommitmentError("Index out of bounds")
         return KZGCommitment.open_evaluations_batch(params, vectors, index, raw)
+
+    @staticmethod
+    def open_batch_indices(params: CommitmentParams, vectors, indices, raw: bool = False):
+        """open(params, vectors[b], indices[b]) of every vector at its own index: (values, proofs) as
+        KZGCommitment.open_evaluations_batch_points returns them."""
+        n = len(vectors[0]) if len(vectors) else 0
+        indices = [int(i) for i in indices]
+        if len(indices) != len(vectors):
+            raise InvalidParameters("one index per vector")
+        if any(not 0 <= i < n for i in indices):
+            raise CommitmentError("Index out of bounds")
+        return KZGCommitment.open_evaluations_batch_points(params, vectors, indices, raw)
 
     @staticmethod
     def open_all(params: CommitmentParams, vector) -> np.ndarray:
@@ -1283,6 +1310,38 @@ class Twist:
     def prove(self, trace: MemoryTrace) -> TwistProof:
         return self.prove_soa(*trace.soa())
 
+    def prove_soa_batch(self, addr: np.ndarray, value: np.ndarray, is_write: np.ndarray) -> List[TwistProof]:
+        """prove_soa of every row of a batch of equally long traces in one call (tns_twist_prove_batch):
+        addr (B, n) u64, value (B, n, 4) Montgomery limbs, is_write (B, n) bytes."""
+        pp = self.prover_params
+        srs = pp.commitment_params.srs
+        addr = np.ascontiguousarray(addr, dtype=np.uint64)
+        if addr.ndim != 2:
+            raise InvalidParameters("addr must be (batch, n_ops)")
+        b, n = addr.shape
+        value = np.ascontiguousarray(value, dtype=np.uint64).reshape(-1, 4)
+        is_write = np.ascontiguousarray(is_write, dtype=np.uint8).reshape(-1)
+        if len(value) != b * n or len(is_write) != b * n:
+            raise InvalidParameters("the traces of a batch must have one length")
+        prs = (N.TnsProof * max(b, 1))()
+        _check(N.load().tns_twist_prove_batch(
+            srs.ctx.handle, srs.handle, C.byref(pp.raw()),
+            N.p64(addr.reshape(-1) if b * n else np.zeros(1, dtype=np.uint64)), N.p64(_nonempty(value)),
+            N.p8(is_write if b * n else np.zeros(1, dtype=np.uint8)), n, b, prs))
+        return [twist_proof_from_raw(prs[i]) for i in range(b)]
+
+    def prove_batch(self, traces: Sequence[MemoryTrace]) -> List[TwistProof]:
+        """prove(trace) of every trace in one call; the traces must have one length."""
+        soas = [t.soa() for t in traces]
+        if not soas:
+            return []
+        if any(len(s[0]) != len(soas[0][0]) for s in soas):
+            raise InvalidParameters("the traces of a batch must have one length")
+        n = len(soas[0][0])
+        return self.prove_soa_batch(np.stack([np.asarray(s[0], dtype=np.uint64).reshape(n) for s in soas]),
+                                    np.stack([np.asarray(s[1], dtype=np.uint64).reshape(n, 4) for s in soas]),
+                                    np.stack([np.asarray(s[2], dtype=np.uint8).reshape(n) for s in soas]))
+
     @staticmethod
     def verify(proof: TwistProof, verifier_params: VerifierParams) -> bool:
         """src/twist.rs:255-304 (host: sum-check replay + two pairing checks)."""
@@ -1408,6 +1467,36 @@ class Shout:
         ix = np.array([l.index for l in table.lookups], dtype=np.uint64)
         return self.prove_arrays(e, ix)
 
+    def prove_arrays_batch(self, entries_mont: np.ndarray, indices: np.ndarray) -> List[ShoutProof]:
+        """prove_arrays of every (table, lookups) pair of a batch of one shape in one call
+        (tns_shout_prove_batch): entries_mont (B, n_entries, 4) Montgomery limbs, indices (B, n_lookups)."""
+        pp = self.prover_params
+        srs = pp.commitment_params.srs
+        ix = np.ascontiguousarray(indices, dtype=np.uint64)
+        e = np.ascontiguousarray(entries_mont, dtype=np.uint64)
+        if ix.ndim != 2 or e.ndim != 3 or e.shape[0] != ix.shape[0] or e.shape[2] != 4:
+            raise InvalidParameters("entries must be (batch, n_entries, 4) and indices (batch, n_lookups)")
+        b, n_lookups = ix.shape
+        n_entries = e.shape[1]
+        prs = (N.TnsProof * max(b, 1))()
+        _check(N.load().tns_shout_prove_batch(
+            srs.ctx.handle, srs.handle, C.byref(pp.raw()), N.p64(_nonempty(e.reshape(-1, 4))), n_entries,
+            N.p64(ix.reshape(-1) if ix.size else np.zeros(1, dtype=np.uint64)), n_lookups, b, prs))
+        return [shout_proof_from_raw(prs[i]) for i in range(b)]
+
+    def prove_batch(self, tables: Sequence[LookupTable]) -> List[ShoutProof]:
+        """prove(table) of every table in one call; the tables must have one size and one lookup count."""
+        tables = list(tables)
+        if not tables:
+            return []
+        ne, nl = len(tables[0].entries), len(tables[0].lookups)
+        if any(len(t.entries) != ne or len(t.lookups) != nl for t in tables):
+            raise InvalidParameters("the tables of a batch must have one size and one lookup count")
+        flat = [x for t in tables for x in t.entries]
+        e = (to_mont(flat) if flat else np.zeros((0, 4), dtype=np.uint64)).reshape(len(tables), ne, 4)
+        ix = np.array([[l.index for l in t.lookups] for t in tables], dtype=np.uint64).reshape(len(tables), nl)
+        return self.prove_arrays_batch(e, ix)
+
 
 class DeviceBuffer:
     """An input array resident in HBM (tns_buffer_upload)."""
@@ -1469,6 +1558,38 @@ def shout_prove_resident(pp: ProverParams, entries: DeviceBuffer, n_entries: int
     _check(N.load().tns_shout_prove_device(srs.ctx.handle, srs.handle, C.byref(pp.raw()), entries.ptr, n_entries,
                                            indices.ptr, n_lookups, C.byref(pr)))
     return pr
+
+
+def twist_prove_batch_resident(pp: ProverParams, addr: DeviceBuffer, value: DeviceBuffer, is_write: DeviceBuffer,
+                               n_ops: int, batch: int):
+    """tns_twist_prove_batch_device on row-major traces resident in HBM: the array of `batch` raw C proofs."""
+    srs = pp.commitment_params.srs
+    prs = (N.TnsProof * max(batch, 1))()
+    _check(N.load().tns_twist_prove_batch_device(srs.ctx.handle, srs.handle, C.byref(pp.raw()), addr.ptr, value.ptr,
+                                                 is_write.ptr, n_ops, batch, prs))
+    return prs
+
+
+def shout_prove_batch_resident(pp: ProverParams, entries: DeviceBuffer, n_entries: int, indices: DeviceBuffer,
+                               n_lookups: int, batch: int):
+    """tns_shout_prove_batch_device on resident row-major tables and lookups: the array of raw C proofs."""
+    srs = pp.commitment_params.srs
+    prs = (N.TnsProof * max(batch, 1))()
+    _check(N.load().tns_shout_prove_batch_device(srs.ctx.handle, srs.handle, C.byref(pp.raw()), entries.ptr, n_entries,
+                                                 indices.ptr, n_lookups, batch, prs))
+    return prs
+
+
+def open_evaluations_batch_points_resident(params: CommitmentParams, rows: DeviceBuffer, n: int, batch: int, points):
+    """KZGCommitment.open_evaluations_batch_points on resident rows: (values as ints, the (batch, 8) limb array)."""
+    srs = params.srs
+    v = np.zeros((max(batch, 1), 4), dtype=np.uint64)
+    z = to_mont([int(p) for p in points]) if batch else np.zeros((1, 4), dtype=np.uint64)
+    if len(z) != max(batch, 1):
+        raise InvalidParameters("one opening point per row")
+    pis = _batch_points(lambda out: N.load().tns_kzg_open_evals_batch_points_device(
+        srs.ctx.handle, srs.handle, rows.ptr, n, batch, N.p64(z), N.p64(v), out), batch, True, None)
+    return from_mont(v[:batch]), pis
 
 
 def msm_resident(params: CommitmentParams, scalars: DeviceBuffer, n: int) -> np.ndarray:

@@ -151,6 +151,21 @@ SIGNATURES = [
     ("tns_kzg_commit_evals_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P]),
     ("tns_kzg_open_evals_batch_device", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P, U64P, U64P]),
+    ("tns_kzg_open_evals_batch_points", C.c_int,
+     [C.c_void_p, C.c_void_p, U64P, C.c_size_t, C.c_size_t, U64P, U64P, U64P]),
+    ("tns_kzg_open_evals_batch_points_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P, U64P, U64P]),
+    ("tns_twist_prove_batch", C.c_int,
+     [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), U64P, U64P, U8P, C.c_size_t, C.c_size_t, C.POINTER(TnsProof)]),
+    ("tns_twist_prove_batch_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+      C.POINTER(TnsProof)]),
+    ("tns_shout_prove_batch", C.c_int,
+     [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), U64P, C.c_size_t, U64P, C.c_size_t, C.c_size_t,
+      C.POINTER(TnsProof)]),
+    ("tns_shout_prove_batch_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+      C.POINTER(TnsProof)]),
     ("tns_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("tns_profile_only", C.c_int, [C.c_void_p, C.c_char_p]),
     ("tns_profile_read_ex", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
