@@ -1,5 +1,5 @@
-// abi.hpp -- what the translation units of the C ABI (api.hip, kzg.hip, prove.hip, abi_host.cpp)
-// share: the opaque handle types of include/tns.h, the error guard of every entry point, and the
+// abi.hpp -- what the translation units of the C ABI (api.hip, kzg.hip, kzg_batch.hip, prove.hip,
+// prove_batch.hip, abi_host.cpp) share: the opaque handle types of include/tns.h, the error guard of every entry point, and the
 // KZG routes of kzg.hip.
 #pragma once
 #include <chrono>
@@ -159,5 +159,16 @@ bool kzg_verify_many_dev(Ctx *c, const Vk &vk, const VerifyBatch &in, const uint
 // prove.hip
 void check_shard(const Comm &m, size_t N, const char *what);
 size_t slice_count(uint64_t n_total, size_t first, size_t L);
+// What the transcript alone decides of a Twist / Shout proof, for the single and the batched
+// provers: the two commitments appended under their labels, the nv all-zero sum-check rounds
+// (sumcheck_constant_rounds) and, when nv >= 1, the opening point opening_challenges_0, which is
+// returned.  Stores the commitments, num_rounds, the zero round polynomials, the challenges, the
+// zero final evaluation and the opening point into *out, and the challenges into chal[0 .. nv) as
+// well (the caller's memory: the single prover's fold chain copies them from pinned memory).
+Fr zero_closure_transcript(const char *label0, const char *label1, const G1Affine cm[2], unsigned nv, Fr *chal,
+                           tns_proof *out);
+// LookupTable::lookup bounds (src/shout.rs:44-50): whether some idx[i] >= bound (n device values).
+// Zeroes the device word `bad`, runs the check on st, copies the word back and waits for st.
+bool index_out_of_bounds(hipStream_t st, const uint64_t *idx, size_t n, uint64_t bound, unsigned *bad);
 
 }  // namespace tns

@@ -584,9 +584,9 @@ static int sumcheck_prove_core(tns_ctx *ctx, Fr *const *ptrs, int n_tables, unsi
   Fr cl;
   std::memcpy(&cl, claimed, 32);
   std::vector<Fr> rounds(4 * (size_t)(nv ? nv : 1)), chal(nv ? nv : 1);
-  Fr finals[4], fe;
+  Fr fe;
   int rc = sumcheck_prove_dev(&ctx->c, ptrs, n_tables, nv, cl, st.data(), n_terms, tr->t, rounds.data(),
-                              chal.data(), finals, &fe);
+                              chal.data(), &fe);
   std::memcpy(rounds_out, rounds.data(), 128 * (size_t)nv);
   if (challenges_out) std::memcpy(challenges_out, chal.data(), 32 * (size_t)nv);
   std::memcpy(final_out, &fe, 32);

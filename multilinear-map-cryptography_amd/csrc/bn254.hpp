@@ -719,7 +719,7 @@ __device__ __forceinline__ bool fq_zero_lazy(const Fq &a) {
 // K - a for a constant K >= a (no borrow out, no correction): K = M negates a canonical value,
 // K = 2M forms the lazy-domain negation of a value in [0, 2M): the result lies in (0, 2M], and it
 // is 2M itself -- outside [0, 2M) -- exactly for a = 0.  The point formulas below pass values that
-// are nonzero mod M (PPP, W of a finite, non-doubling step), so theirs stay below 2M; mle.hip's
+// are nonzero mod M (PPP, W of a finite, non-doubling step), so theirs stay below 2M; sumcheck.hip's
 // round kernel works in the closed [0, 2M], which every lazy function here maps into itself.
 // a in [0, K] in either case.  a is tied to the result (no
 // early-clobber operand, see field_asm.inc); the borrow-chain limbs of K come from VGPRs (one

@@ -1,6 +1,6 @@
 // ctx.hpp -- the per-device context: its streams, its named device workspaces and caches, the lock
 // every entry point takes, the host-input uploader, and the entry points of the modules that work
-// on the context alone (mle.hip, poly.hip, interp.hip).
+// on the context alone (mle.hip, sumcheck.hip, zero_folds.hip, poly.hip, interp.hip).
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -69,9 +69,9 @@ class SharedScratch {
   DevBuf slot[SCAN_LEVELS];
 };
 
-// The sum-check's workspaces (mle.hip).  The generic prover (sumcheck_prove_dev,
-// composition_sum_dev) runs on Ctx::stream; the zero-closure fold chain of Twist / Shout::prove
-// (sumcheck_zero_folds_async) on Ctx::side.
+// The sum-check's workspaces.  The generic prover (sumcheck.hip: sumcheck_prove_dev,
+// composition_sum_dev) runs on Ctx::stream; the single zero-closure fold chain of Twist /
+// Shout::prove (zero_folds.hip: sumcheck_zero_folds_async) on Ctx::side.
 struct SumcheckWs {
   // second fold buffer per table (the input tables stay intact).  Both provers use it: the prove
   // cores drain the side stream before they start and before they return (prove.hip SideDrain),
@@ -79,9 +79,8 @@ struct SumcheckWs {
   DevBuf pong[4];
   DevBuf half[4], chal, out;      // the zero-closure fold chain on the side stream
   DevBuf partials;                // the round kernels' per-block sums (bounded by their grids)
-  DevBuf fold_out;                // the generic prover's bound table values (k_sc_fold_tail)
   DevBuf counter;                 // round kernel: last-workgroup counter
-  DevBuf poly;                    // ... and its composition (ScPoly, mle.hip)
+  DevBuf poly;                    // ... and its composition (ScPoly, sumcheck.hip)
   PinnedBuf poly_host;            // (its host staging copy)
   MappedHostBuf mapped;           // round results + flag, polled by the host
   MappedHostBuf htab;             // the folded tables of the host's last rounds
@@ -212,24 +211,45 @@ struct CtxScope {
 // mle.hip
 void mle_fold_dev(Ctx *c, const Fr *in, Fr *out, size_t half, const Fr &r);
 Fr mle_evaluate_dev(Ctx *c, const Fr *evals, unsigned nv, const Fr *point_host);
+
+// sumcheck.hip
 struct SumcheckTerm {
   Fr coeff;
   int tab[3];
 };
-// Runs every round of SumCheck::prove over k device tables of 2^nv entries
-// (consumed: they are folded in place into workspace).  Transcript callback is
-// host-side.  Returns status; fills rounds (nv x 4), challenges, final values.
 struct HostTranscript;
-// The zero-closure fold chain (mle.hip): binds the k tables at the challenges on stream st and
-// writes their values to d_out.  flags (optional): the last table as 0/1 bytes (n_flags of
-// them, zero beyond), tables[k - 1] unused -- only when sumcheck_folds_take_flag_bytes(nv).
+Fr composition_sum_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const SumcheckTerm *terms, int n_terms);
+// Runs every round of SumCheck::prove over k device tables of 2^nv entries (only read: they are
+// folded into workspace) on the host's transcript.  Returns status; fills rounds (nv x 4), the
+// challenges and the final evaluation.
+int sumcheck_prove_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const Fr &claimed,
+                       const SumcheckTerm *terms, int n_terms, HostTranscript &tr, Fr *rounds,
+                       Fr *challenges, Fr *final_eval);
+// The nv rounds of a closure that is the constant c everywhere (c = 0: the zero closure of Twist /
+// Shout), on the transcript alone; rounds (nv x 4) and chal (nv) are optional.
+void sumcheck_constant_rounds(HostTranscript &tr, unsigned nv, const Fr &c, Fr *rounds, Fr *chal);
+
+// zero_folds.hip
+// The single chain: binds the k tables at the challenges on stream st and writes their values to
+// d_out.  flags (optional): the last table as 0/1 bytes (n_flags of them, zero beyond),
+// tables[k - 1] unused -- only when sumcheck_folds_take_flag_bytes(nv).
 bool sumcheck_folds_take_flag_bytes(unsigned nv);
 void sumcheck_zero_folds_async(Ctx *c, hipStream_t st, Fr *const *tables, int k, unsigned nv, const Fr *chal_pinned,
                                Fr *d_out, const uint8_t *flags = nullptr, size_t n_flags = 0);
-Fr composition_sum_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const SumcheckTerm *terms, int n_terms);
-int sumcheck_prove_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const Fr &claimed,
-                       const SumcheckTerm *terms, int n_terms, HostTranscript &tr, Fr *rounds,
-                       Fr *challenges, Fr *final_table_values, Fr *final_eval);
+// The batched chain's inputs: up to two Fr tables of `rows` x N entries and, last, the op-type
+// table as 0/1 bytes (n_flags a row, zero beyond).
+struct FoldIn {
+  const Fr *tab[2];
+  const uint8_t *flags;
+  size_t n_flags;
+  int n_fr;  // Fr tables; the flag table (if any) is table n_fr
+};
+constexpr size_t FOLD_TAIL = 512;  // entries a block of the chain's last kernel binds in LDS
+// all ntab tables of all `rows` proofs (2^nv = N entries each) bound at their proofs' challenges
+// d_chal[b nv + k] into d_finals[b ntab + t]; f0 / f1: rows ntab N/2 and rows ntab N/4 entries of
+// scratch (unused when N <= FOLD_TAIL)
+void fold_batch(Ctx *c, const FoldIn &in, int ntab, size_t N, size_t rows, unsigned nv, const Fr *d_chal, Fr *f0, Fr *f1,
+                Fr *d_finals);
 
 // poly.hip
 // q[i] = c[i+1] + z q[i+1] (synthetic division by x - z); returns P(z).  q may be null.

@@ -3,7 +3,7 @@
 // Twist::prove (src/twist.rs:107-252) and Shout::prove (src/shout.rs:97-222) run with
 // every bulk vector resident in HBM: one H2D of the trace, exact interpolation
 // (interp.hip), two KZG commits (msm.hip), the host transcript, the sum-check fold
-// chain (mle.hip), then the two openings (poly.hip synthetic division + msm.hip).
+// chain (zero_folds.hip), then the two openings (poly.hip synthetic division + msm.hip).
 // Only commitments, 4-element round polynomials and challenges cross PCIe.
 #include "abi.hpp"
 
@@ -19,6 +19,53 @@ size_t slice_count(uint64_t n_total, size_t first, size_t L) {
   return n_total <= first ? 0 : (size_t)std::min<uint64_t>(L, n_total - first);
 }
 
+// The zero constraint closure (src/twist.rs:186-214, src/shout.rs:160-184) makes every round
+// polynomial [0, 0, 0, 0] and final_evaluation 0 (src/sumcheck.rs:77-104), so the transcript alone
+// -- the two commitments under the protocol's labels, then the nv zero rounds -- yields the
+// challenges, and the opening point after them.
+Fr zero_closure_transcript(const char *label0, const char *label1, const G1Affine cm[2], unsigned nv, Fr *chal,
+                           tns_proof *out) {
+  store_proj(cm[0], out->commitments[0]);
+  store_proj(cm[1], out->commitments[1]);
+  HostTranscript tr;
+  tr.append_label(label0);
+  tr.append_fr(commitment_hash(cm[0]));
+  tr.append_label(label1);
+  tr.append_fr(commitment_hash(cm[1]));
+  sumcheck_constant_rounds(tr, nv, Fr::zero(), nullptr, chal);
+  out->num_rounds = nv;
+  std::memset(out->round_polynomials, 0, 128 * (size_t)nv);  // (a tns_proof's words are not aligned as Fr)
+  std::memcpy(out->sumcheck_challenges, chal, 32 * (size_t)nv);
+  std::memset(out->final_evaluation, 0, 32);
+  // challenge_field_elements("opening_challenges", nv) (src/utils.rs:195-203); only [0] is used
+  // (src/twist.rs:219-226, src/shout.rs:189-195), and elements 1..nv-1 only extend a transcript
+  // that nothing reads afterwards, so they are not derived (no observable output depends on
+  // them; ~0.1 ms of host hashing in front of the openings at nv = 24)
+  Fr z = Fr::zero();
+  if (nv >= 1) {
+    z = tr.challenge("opening_challenges_0");
+    std::memcpy(out->opening_point, &z, 32);
+  }
+  return z;
+}
+
+// LookupTable::lookup bounds (src/shout.rs:44-50): whether some idx[i] >= bound.  Zeroes the
+// device word `bad`, runs the check on st, copies the word back and waits for st.
+__global__ void k_max_index_check(const uint64_t *__restrict__ idx, size_t n, uint64_t bound,
+                                  unsigned *__restrict__ bad) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    if (idx[i] >= bound) *bad = 1;
+}
+bool index_out_of_bounds(hipStream_t st, const uint64_t *idx, size_t n, uint64_t bound, unsigned *bad) {
+  unsigned hbad = 0;
+  TNS_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned), st));
+  k_max_index_check<<<grid_for(n, 256), 256, 0, st>>>(idx, n, bound, bad);
+  TNS_LAUNCH_CHECK();
+  TNS_HIP(hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, st));
+  TNS_HIP(hipStreamSynchronize(st));
+  return hbad != 0;
+}
+
 }  // namespace tns
 
 using namespace tns;
@@ -31,28 +78,20 @@ extern "C" {
 // src/polynomials.rs:111-119), so they run locally; the last log2(size) rounds run on
 // the host over the one folded value per table and rank (allgathered).
 // flags (optional): the last of the mles as 0/1 bytes (sumcheck_zero_folds_async)
-static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *const *mles, int n_mles,
-                             unsigned nv, EvalPoly &polyA, EvalPoly &polyB, tns_proof *out, double *timing,
-                             Comm &m, const uint8_t *flags = nullptr, size_t n_flags = 0) {
+static void fill_common_tail(Ctx *c, const Srs &srs, const G1Affine cm[2], const char *label0, const char *label1,
+                             Fr *const *mles, int n_mles, unsigned nv, EvalPoly &polyA, EvalPoly &polyB,
+                             tns_proof *out, double *timing, Comm &m, const uint8_t *flags = nullptr,
+                             size_t n_flags = 0) {
   Timer t_sc;
   unsigned lr = 0;
   while ((1 << lr) < m.size) lr++;
   const unsigned nv_loc = nv - lr;  // check_shard guarantees size <= 2^nv
   if (n_mles < 1 || n_mles > 3) throw Error(TNS_ERR_INVALID_PARAMETERS, "1 to 3 trace tables");
-  // The zero constraint closure (src/twist.rs:186-214, src/shout.rs:160-184) makes every round
-  // polynomial [0, 0, 0, 0] and final_evaluation 0 (src/sumcheck.rs:77-104), so the transcript
-  // alone yields the challenges: all nv rounds run on the host first ...
+  // all nv rounds run on the host first (the challenges stay in pinned memory: the folds' async
+  // copy reads them) ...
   const unsigned nv1 = nv ? nv : 1;
-  std::vector<Fr> rounds(4 * (size_t)nv1, Fr::zero());
   Fr *chal = (Fr *)c->sc.host.ensure(sizeof(Fr) * (nv1 + 4)), *vals = chal + nv1;
-  char lab[64];
-  for (unsigned rnd = 0; rnd < nv; rnd++) {
-    snprintf(lab, sizeof lab, "sumcheck_round_%u", rnd);  // src/sumcheck.rs:90-96
-    tr.append_label(lab);
-    for (int x = 0; x < 4; x++) tr.append_fr(Fr::zero());
-    snprintf(lab, sizeof lab, "sumcheck_challenge_%u", rnd);
-    chal[rnd] = tr.challenge(lab);
-  }
+  const Fr z = zero_closure_transcript(label0, label1, cm, nv, chal, out);
   // ... and the folds binding this rank's tables at r_0 .. r_{nv_loc-1} (the MLE values the
   // closure evaluates, src/sumcheck.rs:104) run on the side stream under the openings; their
   // values are collected at the end of the proof
@@ -69,16 +108,7 @@ static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *con
     sumcheck_zero_folds_async(c, c->side, mles, n_mles, nv_loc, chal, d_vals, flags, n_flags);
     TNS_HIP(hipMemcpyAsync(vals, d_vals, sizeof(Fr) * n_mles, hipMemcpyDeviceToHost, c->side));
   };
-  const Fr fe = Fr::zero();
-  out->num_rounds = nv;
-  std::memcpy(out->round_polynomials, rounds.data(), 128 * (size_t)nv);
-  std::memcpy(out->sumcheck_challenges, chal, 32 * (size_t)nv);
-  std::memcpy(out->final_evaluation, &fe, 32);
   timing[3] = t_sc.ms();
-  // challenge_field_elements("opening_challenges", nv) (src/utils.rs:195-203); only [0] is used
-  // (src/twist.rs:219-226, src/shout.rs:189-195), and elements 1..nv-1 only extend a transcript
-  // that nothing reads afterwards, so they are not derived (no observable output depends on
-  // them; ~0.1 ms of host hashing in front of the openings at nv = 24)
   Timer t_open;
   // sharded: every rank's folded values travel with the opening partials (one exchange, not two)
   Fr finals[3];
@@ -92,8 +122,6 @@ static void fill_common_tail(Ctx *c, const Srs &srs, HostTranscript &tr, Fr *con
     for (int j = 0; j < n_mles; j++) finals[j] = vals[j];
   };
   if (nv >= 1) {
-    Fr z = tr.challenge("opening_challenges_0");
-    std::memcpy(out->opening_point, &z, 32);
     Fr v[2];
     G1Affine pi[2];
     open_evals_pair(c, srs, polyA, polyB, z, v, pi, c->prove.open_s[0], c->prove.open_s[1], m, lr ? &fold_x : nullptr,
@@ -132,12 +160,6 @@ __global__ void k_write_flags(const uint8_t *__restrict__ in, Fr *__restrict__ o
     out[i] = (i < n_in && in[i]) ? Fr::one() : Fr::zero();
 }
 
-__global__ void k_max_index_check(const uint64_t *__restrict__ idx, size_t n, uint64_t bound,
-                                  unsigned *__restrict__ bad) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    if (idx[i] >= bound) *bad = 1;
-}
-
 // The node ranges the drop-in values arrive in: k equal ranges (Ctx::upload_chunks).  (Splitting the
 // last one in two, so the MSM left after the upload is an eighth of the vector, measured equal at
 // C4: 56.4-57.5 vs 56.4-57.9 ms per drop-in proof, profiles/r04_ab_upload_split.txt.)
@@ -157,20 +179,14 @@ struct SideDrain {
   ~SideDrain() { (void)hipStreamSynchronize(c->side); }
 };
 
-// The close of both prove cores: the two commitments into the proof and the transcript (under the
-// protocol's labels), the sum-check and the openings, and the wait for the context stream.
+// The close of both prove cores: the transcript of the two commitments (under the protocol's
+// labels), the sum-check and the openings, and the wait for the context stream.
 static void finish_proof(tns_ctx *ctx, const Srs &srs, const Timer &total, const G1Affine cm[2], const char *label0,
                          const char *label1, Fr *const *mles, int n_mles, unsigned nv, EvalPoly &polyA,
                          EvalPoly &polyB, tns_proof *out, Comm &m, const uint8_t *flags = nullptr,
                          size_t n_flags = 0) {
-  store_proj(cm[0], out->commitments[0]);
-  store_proj(cm[1], out->commitments[1]);
-  HostTranscript tr;
-  tr.append_label(label0);
-  tr.append_fr(commitment_hash(cm[0]));
-  tr.append_label(label1);
-  tr.append_fr(commitment_hash(cm[1]));
-  fill_common_tail(&ctx->c, srs, tr, mles, n_mles, nv, polyA, polyB, out, ctx->timing, m, flags, n_flags);
+  fill_common_tail(&ctx->c, srs, cm, label0, label1, mles, n_mles, nv, polyA, polyB, out, ctx->timing, m, flags,
+                   n_flags);
   TNS_HIP(hipStreamSynchronize(ctx->c.stream));
   ctx->timing[5] = total.ms();
 }
@@ -390,12 +406,7 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
       upload.wait(up_i, st);
       widen_dev(st, dir32, upload.narrow_width(up_i), n_lookups, const_cast<uint64_t *>(ir));
     }
-    unsigned *bad = (unsigned *)w.flags.ensure(sizeof(unsigned));
-    TNS_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned), st));
-    k_max_index_check<<<grid_for(n_lookups, 256), 256, 0, st>>>(ir, n_lookups, n_entries_total, bad);
-    TNS_LAUNCH_CHECK();
-    TNS_HIP(hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, st));
-    TNS_HIP(hipStreamSynchronize(st));
+    hbad = index_out_of_bounds(st, ir, n_lookups, n_entries_total, (unsigned *)w.flags.ensure(sizeof(unsigned)));
   }
   // (sharded: every rank's verdict travels with the commitments' partial sums and all ranks fail
   // together after that exchange -- the MSMs read the indices as scalars only, so an out-of-range
@@ -421,7 +432,7 @@ static void shout_core(tns_ctx *ctx, const tns_srs *srs, const tns_params *param
   pt.coeffs = m.size == 1 ? (Fr *)w.coeff[0].ensure(sizeof(Fr) * T) : nullptr;
   pi.coeffs = m.size == 1 ? (Fr *)w.coeff[1].ensure(sizeof(Fr) * M) : nullptr;
   pt.y = TB;
-  pi.y = I;  // the sum-check leaves its input tables intact (mle.hip)
+  pi.y = I;  // the sum-check leaves its input tables intact (zero_folds.hip)
   tm[1] = t_int.ms();
   Timer t_com;
   G1Affine cm[2];

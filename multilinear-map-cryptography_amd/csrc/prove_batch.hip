@@ -6,10 +6,11 @@
 // is the cost.  Here every stage runs once for all proofs:
 //   tables   one row-aware kernel writes the Montgomery address / index rows, zero-padded to N;
 //   commit   commit_evals_batch (kzg_batch.hip) of the narrow rows and of the full-width rows;
-//   host     one transcript per proof: all batch * nv challenges and all opening points exist
-//            before a fold or an opening is queued, and reach the device in one copy;
+//   host     one transcript per proof (zero_closure_transcript, prove.hip): all batch * nv
+//            challenges and all opening points exist before a fold or an opening is queued, and
+//            reach the device in one copy;
 //   folds    T'[s] = T[2s] + r_{b,k} (T[2s+1] - T[2s]) for every proof and table, one launch per
-//            round down to 512 entries, then one launch for the rest;
+//            round down to 512 entries, then one launch for the rest (fold_batch, zero_folds.hip);
 //   open     open_evals_batch_points with two rows a point (a proof's two vectors share z).
 // Every proof is byte for byte what the single prover returns for its row.  prove_batch_plan.hpp
 // decides the route; on the rows route the single prover runs row by row.
@@ -28,109 +29,7 @@ __global__ void __launch_bounds__(256) k_rows_u64_tables(const uint64_t *__restr
   }
 }
 
-// LookupTable::lookup bounds (src/shout.rs:44-50) over every row's indices
-__global__ void __launch_bounds__(256) k_rows_index_check(const uint64_t *__restrict__ idx, size_t total,
-                                                          uint64_t bound, unsigned *__restrict__ bad) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
-    if (idx[i] >= bound) *bad = 1;
-}
-
-// The fold inputs of one call: up to two Fr tables of `rows` x N entries and, last, the op-type
-// table as 0/1 bytes (n_flags a row, zero beyond).  Table t of proof b, entry i.
-struct FoldIn {
-  const Fr *tab[2];
-  const uint8_t *flags;
-  size_t n_flags;
-  int n_fr;  // Fr tables; the flag table (if any) is table n_fr
-};
-__device__ __forceinline__ Fr fold_load(const FoldIn &in, size_t N, size_t b, int t, size_t i) {
-  if (t < in.n_fr) return in.tab[t][b * N + i];
-  return (i < in.n_flags && in.flags[b * in.n_flags + i]) ? Fr::one() : Fr::zero();
-}
-
-// round 0 of every proof and table: out[(b ntab + t) N/2 + s] = T[2s] + r_{b,0} (T[2s+1] - T[2s])
-__global__ void __launch_bounds__(256) k_fold_first(FoldIn in, int ntab, size_t N, size_t rows, unsigned nv,
-                                                    const Fr *__restrict__ chal, Fr *__restrict__ out) {
-  const size_t h = N / 2, total = rows * ntab * h;
-  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const size_t bt = e / h, s = e - bt * h, b = bt / ntab;
-    const int t = (int)(bt - b * ntab);
-    const Fr lo = fold_load(in, N, b, t, 2 * s), hi = fold_load(in, N, b, t, 2 * s + 1);
-    out[e] = add(lo, mul(chal[b * nv + 0], sub(hi, lo)));
-  }
-}
-
-// round k on the packed tables: src holds `tabs` tables of cur entries, dst tabs tables of cur / 2
-__global__ void __launch_bounds__(256) k_fold_round(const Fr *__restrict__ src, size_t cur, size_t tabs, int ntab,
-                                                    unsigned nv, unsigned k, const Fr *__restrict__ chal,
-                                                    Fr *__restrict__ dst) {
-  const size_t h = cur / 2, total = tabs * h;
-  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const size_t bt = e / h, s = e - bt * h, b = bt / ntab;
-    const Fr lo = src[bt * cur + 2 * s], hi = src[bt * cur + 2 * s + 1];
-    dst[e] = add(lo, mul(chal[b * nv + k], sub(hi, lo)));
-  }
-}
-
-constexpr size_t FOLD_TAIL = 512;  // entries a block of k_fold_tail binds in LDS
-static_assert(FOLD_TAIL / 2 <= 256, "a round of k_fold_tail is one entry a thread of its 256");
-
-// the rounds k0 .. nv-1 of tables of cur = 2^(nv-k0) <= FOLD_TAIL entries, a block a table:
-// finals[b ntab + t] = the table's value at the proof's challenges.  FIRST: cur = N, from the inputs.
-template <bool FIRST>
-__global__ void __launch_bounds__(256) k_fold_tail(FoldIn in, const Fr *__restrict__ src, size_t cur, size_t tabs,
-                                                   int ntab, unsigned nv, unsigned k0, const Fr *__restrict__ chal,
-                                                   Fr *__restrict__ finals) {
-  __shared__ Fr lds[FOLD_TAIL];
-  for (size_t bt = blockIdx.x; bt < tabs; bt += gridDim.x) {
-    const size_t b = bt / ntab;
-    const int t = (int)(bt - b * ntab);
-    for (size_t i = threadIdx.x; i < cur; i += 256) lds[i] = FIRST ? fold_load(in, cur, b, t, i) : src[bt * cur + i];
-    __syncthreads();
-    unsigned k = k0;
-    for (size_t h = cur / 2; h >= 1; h >>= 1, k++) {
-      const Fr r = chal[b * nv + k];
-      const size_t s = threadIdx.x;  // h <= FOLD_TAIL / 2 = blockDim.x
-      Fr v = Fr::zero();
-      if (s < h) v = add(lds[2 * s], mul(r, sub(lds[2 * s + 1], lds[2 * s])));
-      __syncthreads();
-      if (s < h) lds[s] = v;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) finals[bt] = lds[0];
-    __syncthreads();
-  }
-}
-
 namespace {
-
-// all tables of all proofs bound at their proofs' challenges (LSB-first); the inputs stay intact
-void fold_batch(Ctx *c, const FoldIn &in, int ntab, size_t N, size_t rows, unsigned nv, const Fr *d_chal, Fr *f0, Fr *f1,
-                Fr *d_finals) {
-  TNS_PROF(c, "sumcheck_round", 32.0 * 2 * rows * ntab * N);
-  hipStream_t st = c->stream;
-  const size_t tabs = rows * (size_t)ntab;
-  const unsigned tail_grid = grid_for(tabs, 1, 1u << 16);
-  if (N <= FOLD_TAIL) {
-    k_fold_tail<true><<<tail_grid, 256, 0, st>>>(in, nullptr, N, tabs, ntab, nv, 0, d_chal, d_finals);
-    TNS_LAUNCH_CHECK();
-    return;
-  }
-  k_fold_first<<<grid_for(tabs * (N / 2), 256, 1u << 16), 256, 0, st>>>(in, ntab, N, rows, nv, d_chal, f0);
-  TNS_LAUNCH_CHECK();
-  size_t cur = N / 2;
-  unsigned k = 1;
-  Fr *src = f0, *dst = f1;
-  while (cur > FOLD_TAIL) {
-    k_fold_round<<<grid_for(tabs * (cur / 2), 256, 1u << 16), 256, 0, st>>>(src, cur, tabs, ntab, nv, k, d_chal, dst);
-    TNS_LAUNCH_CHECK();
-    std::swap(src, dst);
-    cur /= 2;
-    k++;
-  }
-  k_fold_tail<false><<<tail_grid, 256, 0, st>>>(in, src, cur, tabs, ntab, nv, k, d_chal, d_finals);
-  TNS_LAUNCH_CHECK();
-}
 
 // the checks both batched provers share, after the NULL handles; true: nothing to do
 bool prove_batch_checks(const tns_srs *srs, size_t batch, const void *out) {
@@ -194,30 +93,10 @@ void finish_batch(tns_ctx *ctx, const Srs &srs, const BatchedProof &bp, size_t b
   // point before any fold or opening is queued
   Timer t_host;
   std::vector<Fr> chal(batch * (size_t)nv), z(batch);
-  const Fr fe = Fr::zero();
-  char lab[64];
-  for (size_t b = 0; b < batch; b++) {
-    tns_proof *o = &out[b];
-    std::memset(o, 0, sizeof *o);
-    store_proj(cm[0][b], o->commitments[0]);
-    store_proj(cm[1][b], o->commitments[1]);
-    HostTranscript tr;
-    tr.append_label(bp.label[0]);
-    tr.append_fr(commitment_hash(cm[0][b]));
-    tr.append_label(bp.label[1]);
-    tr.append_fr(commitment_hash(cm[1][b]));
-    for (unsigned rnd = 0; rnd < nv; rnd++) {
-      snprintf(lab, sizeof lab, "sumcheck_round_%u", rnd);  // src/sumcheck.rs:90-96
-      tr.append_label(lab);
-      for (int x = 0; x < 4; x++) tr.append_fr(Fr::zero());
-      snprintf(lab, sizeof lab, "sumcheck_challenge_%u", rnd);
-      chal[b * nv + rnd] = tr.challenge(lab);
-    }
-    z[b] = tr.challenge("opening_challenges_0");  // (src/utils.rs:195-203; only [0] is used)
-    o->num_rounds = nv;  // the zero closure's round polynomials and final evaluation: zeros
-    std::memcpy(o->sumcheck_challenges, &chal[b * nv], 32 * (size_t)nv);
-    std::memcpy(o->final_evaluation, &fe, 32);
-    std::memcpy(o->opening_point, &z[b], 32);
+  for (size_t b = 0; b < batch; b++) {  // (nv >= 1 on this route: every proof has an opening point)
+    std::memset(&out[b], 0, sizeof out[b]);
+    const G1Affine cmb[2] = {cm[0][b], cm[1][b]};
+    z[b] = zero_closure_transcript(bp.label[0], bp.label[1], cmb, nv, &chal[b * nv], &out[b]);
   }
   tm[3] = t_host.ms();
   // ---- folds
@@ -294,67 +173,44 @@ void zero_timing(tns_ctx *ctx) {
   for (int i = 0; i < 6; i++) ctx->timing[i] = 0;
 }
 
-}  // namespace
-
-int twist_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *addr,
-                      const uint64_t *value, const uint8_t *is_write, size_t n_ops, size_t batch, tns_proof *out,
-                      bool resident, const BatchLimits &lim, ProveBatchReport *rep_out) {
+// What both batched provers do around their protocol: the checks every call shares, the route, the
+// report, the drain, the timing and the rows route.  The protocol supplies
+//   checks   its own argument checks, in the single prover's order; returns the padded node counts
+//            (wide, narrow) of its two committed vectors;
+//   batched  the batched route: the inputs to the device, its tables, finish_batch;
+//   row      the single prover on row b (it takes the context lock itself).
+int prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, size_t batch, tns_proof *out,
+                const BatchLimits &lim, ProveBatchReport *rep_out,
+                const std::function<std::pair<size_t, size_t>()> &checks,
+                const std::function<void(Ctx *, ProveBatchReport &)> &batched, const std::function<int(size_t)> &row) {
   ProveBatchReport rep;
   rep.route = BATCH_ROUTE_ROWS;
   Timer total;
   int status = guarded([&]() {
     if (!ctx || !srs || !params) throw Error(TNS_ERR_INVALID_PARAMETERS, "null context, SRS or parameters");
     if (prove_batch_checks(srs, batch, out)) return (int)TNS_OK;
-    if (n_ops && (!addr || !value || !is_write)) throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    const size_t N = next_pow2(n_ops);
-    check_scalars(batch, N);
-    if (n_ops > params->max_operations) throw Error(TNS_ERR_INVALID_PARAMETERS, "Too many operations");  // src/twist.rs:108-112
-    const unsigned nv = ilog2_exact(N);
-    if (nv > TNS_MAX_ROUNDS) throw Error(TNS_ERR_INVALID_PARAMETERS, "trace too long");
     ProveBatchShape shape;
     shape.batch = batch;
-    shape.n_wide = shape.n_narrow = N;
+    std::tie(shape.n_wide, shape.n_narrow) = checks();
     {
       CtxScope g(&ctx->c);
       Ctx *c = &ctx->c;
       Drain drain{c};
-      if (N >= 2) shape.basis_wide = shape.basis_narrow = basis_for(c, srs->s, N);
-      const ProveBatchPlan plan = plan_prove_batch(shape, lim);
-      rep.route = plan.route;
-      if (plan.route == BATCH_ROUTE_BATCHED) {
+      if (shape.n_narrow >= 2) {
+        shape.basis_wide = basis_for(c, srs->s, shape.n_wide);
+        shape.basis_narrow = shape.n_wide == shape.n_narrow ? shape.basis_wide : basis_for(c, srs->s, shape.n_narrow);
+      }
+      rep.route = plan_prove_batch(shape, lim).route;
+      if (rep.route == BATCH_ROUTE_BATCHED) {
         zero_timing(ctx);
         TNS_HIP(hipStreamSynchronize(c->side));  // a failed earlier proof's folds may still read the tables
-        DevBuf ab, vb, rb, flb;
-        const uint64_t *d_addr = (const uint64_t *)on_device(c, addr, 8 * batch * n_ops, resident, rb);
-        const uint8_t *d_fl = (const uint8_t *)on_device(c, is_write, batch * n_ops, resident, flb);
-        Fr *A = (Fr *)ab.ensure(sizeof(Fr) * batch * N);
-        k_rows_u64_tables<<<grid_for(batch * N, 256, 1u << 16), 256, 0, c->stream>>>(d_addr, n_ops, N, batch, A);
-        TNS_LAUNCH_CHECK();
-        const Fr *V = padded_rows(c, value, n_ops, N, batch, resident, vb);
-        BatchedProof bp;
-        bp.label[0] = "address_commitment";
-        bp.label[1] = "value_commitment";
-        bp.rows[0] = A;
-        bp.rows[1] = V;
-        bp.nodes[0] = bp.nodes[1] = N;
-        bp.nv = nv;
-        bp.fold.tab[0] = A;
-        bp.fold.tab[1] = V;
-        bp.fold.flags = d_fl;
-        bp.fold.n_flags = n_ops;
-        bp.fold.n_fr = 2;
-        bp.ntab = 3;
-        finish_batch(ctx, srs->s, bp, batch, lim, out, rep);
+        batched(c, rep);
         ctx->timing[5] = total.ms();
         return (int)TNS_OK;
       }
     }
-    // the rows route: the single prover, row by row (each call takes the context lock itself)
     for (size_t b = 0; b < batch; b++) {
-      const int st = resident ? tns_twist_prove_device(ctx, srs, params, addr + b * n_ops, value + 4 * b * n_ops,
-                                                       is_write + b * n_ops, n_ops, &out[b])
-                              : tns_twist_prove(ctx, srs, params, addr + b * n_ops, value + 4 * b * n_ops,
-                                                is_write + b * n_ops, n_ops, &out[b]);
+      const int st = row(b);
       if (st != TNS_OK) return st;  // (its message is the last error)
     }
     zero_timing(ctx);
@@ -365,87 +221,100 @@ int twist_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params
   return status;
 }
 
+}  // namespace
+
+int twist_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *addr,
+                      const uint64_t *value, const uint8_t *is_write, size_t n_ops, size_t batch, tns_proof *out,
+                      bool resident, const BatchLimits &lim, ProveBatchReport *rep_out) {
+  size_t N = 0;
+  auto checks = [&]() {
+    if (n_ops && (!addr || !value || !is_write)) throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
+    N = next_pow2(n_ops);
+    check_scalars(batch, N);
+    if (n_ops > params->max_operations) throw Error(TNS_ERR_INVALID_PARAMETERS, "Too many operations");  // src/twist.rs:108-112
+    if (ilog2_exact(N) > TNS_MAX_ROUNDS) throw Error(TNS_ERR_INVALID_PARAMETERS, "trace too long");
+    return std::make_pair(N, N);
+  };
+  auto batched = [&](Ctx *c, ProveBatchReport &rep) {
+    DevBuf ab, vb, rb, flb;
+    const uint64_t *d_addr = (const uint64_t *)on_device(c, addr, 8 * batch * n_ops, resident, rb);
+    const uint8_t *d_fl = (const uint8_t *)on_device(c, is_write, batch * n_ops, resident, flb);
+    Fr *A = (Fr *)ab.ensure(sizeof(Fr) * batch * N);
+    k_rows_u64_tables<<<grid_for(batch * N, 256, 1u << 16), 256, 0, c->stream>>>(d_addr, n_ops, N, batch, A);
+    TNS_LAUNCH_CHECK();
+    const Fr *V = padded_rows(c, value, n_ops, N, batch, resident, vb);
+    BatchedProof bp;
+    bp.label[0] = "address_commitment";
+    bp.label[1] = "value_commitment";
+    bp.rows[0] = A;
+    bp.rows[1] = V;
+    bp.nodes[0] = bp.nodes[1] = N;
+    bp.nv = ilog2_exact(N);
+    bp.fold.tab[0] = A;
+    bp.fold.tab[1] = V;
+    bp.fold.flags = d_fl;
+    bp.fold.n_flags = n_ops;
+    bp.fold.n_fr = 2;
+    bp.ntab = 3;
+    finish_batch(ctx, srs->s, bp, batch, lim, out, rep);
+  };
+  auto row = [&](size_t b) {
+    return resident ? tns_twist_prove_device(ctx, srs, params, addr + b * n_ops, value + 4 * b * n_ops,
+                                             is_write + b * n_ops, n_ops, &out[b])
+                    : tns_twist_prove(ctx, srs, params, addr + b * n_ops, value + 4 * b * n_ops, is_write + b * n_ops,
+                                      n_ops, &out[b]);
+  };
+  return prove_batch(ctx, srs, params, batch, out, lim, rep_out, checks, batched, row);
+}
+
 int shout_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *entries,
                       size_t n_entries, const uint64_t *indices, size_t n_lookups, size_t batch, tns_proof *out,
                       bool resident, const BatchLimits &lim, ProveBatchReport *rep_out) {
-  ProveBatchReport rep;
-  rep.route = BATCH_ROUTE_ROWS;
-  Timer total;
-  int status = guarded([&]() {
-    if (!ctx || !srs || !params) throw Error(TNS_ERR_INVALID_PARAMETERS, "null context, SRS or parameters");
-    if (prove_batch_checks(srs, batch, out)) return (int)TNS_OK;
+  size_t T = 0, M = 0;
+  auto checks = [&]() {
     if ((n_entries && !entries) || (n_lookups && !indices))
       throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    const size_t T = next_pow2(n_entries), M = next_pow2(n_lookups);  // src/shout.rs:105, :116
+    T = next_pow2(n_entries), M = next_pow2(n_lookups);  // src/shout.rs:105, :116
     check_scalars(batch, std::max(T, M));
     if (n_lookups > params->max_operations)  // src/shout.rs:98-102
       throw Error(TNS_ERR_INVALID_PARAMETERS, "Too many lookup operations");
-    const unsigned nv = ilog2_exact(M);
-    if (nv > TNS_MAX_ROUNDS) throw Error(TNS_ERR_INVALID_PARAMETERS, "too many lookups");
-    ProveBatchShape shape;
-    shape.batch = batch;
-    shape.n_wide = T;
-    shape.n_narrow = M;
-    {
-      CtxScope g(&ctx->c);
-      Ctx *c = &ctx->c;
-      Drain drain{c};
-      if (M >= 2) {
-        shape.basis_wide = basis_for(c, srs->s, T);
-        shape.basis_narrow = T == M ? shape.basis_wide : basis_for(c, srs->s, M);
-      }
-      const ProveBatchPlan plan = plan_prove_batch(shape, lim);
-      rep.route = plan.route;
-      if (plan.route == BATCH_ROUTE_BATCHED) {
-        zero_timing(ctx);
-        TNS_HIP(hipStreamSynchronize(c->side));
-        hipStream_t st = c->stream;
-        DevBuf tb, ib, rb, badb;
-        const uint64_t *d_idx = (const uint64_t *)on_device(c, indices, 8 * batch * n_lookups, resident, rb);
-        // LookupTable::lookup bounds (src/shout.rs:44-50) over all rows: one bad index fails the call
-        unsigned hbad = 0, *bad = (unsigned *)badb.ensure(sizeof(unsigned));
-        TNS_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned), st));
-        k_rows_index_check<<<grid_for(batch * n_lookups, 256), 256, 0, st>>>(d_idx, batch * n_lookups, n_entries, bad);
-        TNS_LAUNCH_CHECK();
-        TNS_HIP(hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, st));
-        TNS_HIP(hipStreamSynchronize(st));
-        if (hbad) throw Error(TNS_ERR_INVALID_PARAMETERS, "Lookup index out of bounds");
-        Fr *I = (Fr *)ib.ensure(sizeof(Fr) * batch * M);
-        k_rows_u64_tables<<<grid_for(batch * M, 256, 1u << 16), 256, 0, st>>>(d_idx, n_lookups, M, batch, I);
-        TNS_LAUNCH_CHECK();
-        const Fr *TB = padded_rows(c, entries, n_entries, T, batch, resident, tb);
-        BatchedProof bp;
-        bp.label[0] = "table_commitment";
-        bp.label[1] = "index_commitment";
-        bp.rows[0] = TB;
-        bp.rows[1] = I;
-        bp.nodes[0] = T;
-        bp.nodes[1] = M;
-        bp.nv = nv;
-        bp.fold.tab[0] = I;  // the closure evaluates only the index MLE (src/shout.rs:175)
-        bp.fold.tab[1] = nullptr;
-        bp.fold.flags = nullptr;
-        bp.fold.n_flags = 0;
-        bp.fold.n_fr = 1;
-        bp.ntab = 1;
-        finish_batch(ctx, srs->s, bp, batch, lim, out, rep);
-        ctx->timing[5] = total.ms();
-        return (int)TNS_OK;
-      }
-    }
-    for (size_t b = 0; b < batch; b++) {
-      const int st = resident ? tns_shout_prove_device(ctx, srs, params, entries + 4 * b * n_entries, n_entries,
-                                                       indices + b * n_lookups, n_lookups, &out[b])
-                              : tns_shout_prove(ctx, srs, params, entries + 4 * b * n_entries, n_entries,
-                                                indices + b * n_lookups, n_lookups, &out[b]);
-      if (st != TNS_OK) return st;
-    }
-    zero_timing(ctx);
-    ctx->timing[5] = total.ms();
-    return (int)TNS_OK;
-  });
-  if (rep_out) *rep_out = rep;
-  return status;
+    if (ilog2_exact(M) > TNS_MAX_ROUNDS) throw Error(TNS_ERR_INVALID_PARAMETERS, "too many lookups");
+    return std::make_pair(T, M);
+  };
+  auto batched = [&](Ctx *c, ProveBatchReport &rep) {
+    hipStream_t st = c->stream;
+    DevBuf tb, ib, rb, badb;
+    const uint64_t *d_idx = (const uint64_t *)on_device(c, indices, 8 * batch * n_lookups, resident, rb);
+    // the bounds over all rows: one bad index fails the call
+    if (index_out_of_bounds(st, d_idx, batch * n_lookups, n_entries, (unsigned *)badb.ensure(sizeof(unsigned))))
+      throw Error(TNS_ERR_INVALID_PARAMETERS, "Lookup index out of bounds");
+    Fr *I = (Fr *)ib.ensure(sizeof(Fr) * batch * M);
+    k_rows_u64_tables<<<grid_for(batch * M, 256, 1u << 16), 256, 0, st>>>(d_idx, n_lookups, M, batch, I);
+    TNS_LAUNCH_CHECK();
+    const Fr *TB = padded_rows(c, entries, n_entries, T, batch, resident, tb);
+    BatchedProof bp;
+    bp.label[0] = "table_commitment";
+    bp.label[1] = "index_commitment";
+    bp.rows[0] = TB;
+    bp.rows[1] = I;
+    bp.nodes[0] = T;
+    bp.nodes[1] = M;
+    bp.nv = ilog2_exact(M);
+    bp.fold.tab[0] = I;  // the closure evaluates only the index MLE (src/shout.rs:175)
+    bp.fold.tab[1] = nullptr;
+    bp.fold.flags = nullptr;
+    bp.fold.n_flags = 0;
+    bp.fold.n_fr = 1;
+    bp.ntab = 1;
+    finish_batch(ctx, srs->s, bp, batch, lim, out, rep);
+  };
+  auto row = [&](size_t b) {
+    return resident ? tns_shout_prove_device(ctx, srs, params, entries + 4 * b * n_entries, n_entries,
+                                             indices + b * n_lookups, n_lookups, &out[b])
+                    : tns_shout_prove(ctx, srs, params, entries + 4 * b * n_entries, n_entries,
+                                      indices + b * n_lookups, n_lookups, &out[b]);
+  };
+  return prove_batch(ctx, srs, params, batch, out, lim, rep_out, checks, batched, row);
 }
 
 }  // namespace tns

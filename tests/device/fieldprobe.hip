@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(64) k_field(const uint32_t *__restrict__ in, u
     reduce_once_2m_dev(a);
     st(y, a);
   }
-  if constexpr (OP == F_CANON2) {  // mle.hip sc_canon: [0, 2M] -> [0, M)
+  if constexpr (OP == F_CANON2) {  // sumcheck.hip sc_canon: [0, 2M] -> [0, M)
     F a = ld<C>(x);
     reduce_once(a);
     reduce_once(a);

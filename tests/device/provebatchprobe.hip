@@ -1,5 +1,5 @@
 // provebatchprobe.hip -- the batched provers' internal entry points (csrc/prove_batch.hip:
-// twist_prove_batch, shout_prove_batch) and the per-row-point openings (csrc/kzg_batch.hip:
+// twist_prove_batch, shout_prove_batch; their folds are csrc/zero_folds.hip's batched chain) and the per-row-point openings (csrc/kzg_batch.hip:
 // open_evals_batch_points) with forced limits, for tests/test_gpu_prove_batch.py and
 // tests/test_gpu_open_batch_points.py: each C entry point calls the shipped function with the
 // BatchLimits it is given and returns the results with the route, groups and group rows that the

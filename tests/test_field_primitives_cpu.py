@@ -62,7 +62,7 @@ def test_operand_sets_cover_the_edges(field):
 
 @field
 def test_lazy_products_stay_in_range(field):
-    """mul_lazy_dev / sqr_lazy_dev: inputs < 2M (<= 2M for Fr, mle.hip) give (a b + m M) / R < 2M."""
+    """mul_lazy_dev / sqr_lazy_dev: inputs < 2M (<= 2M for Fr, sumcheck.hip) give (a b + m M) / R < 2M."""
     f = ref.BY_NAME[field]
     closed = field == "fr"
     pairs = ref.binary_cases(field, f.M2, closed)

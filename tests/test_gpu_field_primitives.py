@@ -174,7 +174,7 @@ def test_add_sub_neg(build, field):
 @build
 @field
 def test_reduce_once(build, field):
-    """reduce_once: [0, 2M) -> [0, M); twice (mle.hip sc_canon): [0, 2M] -> [0, M), for Fr."""
+    """reduce_once: [0, 2M) -> [0, M); twice (sumcheck.hip sc_canon): [0, 2M] -> [0, M), for Fr."""
     f = ref.BY_NAME[field]
     xs = unary(field, f.M2)
     assert (f.M,) in xs and (f.M2 - 1,) in xs
@@ -222,7 +222,7 @@ def test_fq_sqrt_candidate(build):
 @field
 def test_mul_sqr_lazy(build, field):
     f = ref.BY_NAME[field]
-    closed = field == "fr"  # mle.hip: inputs <= 2M give results < 2M
+    closed = field == "fr"  # sumcheck.hip: inputs <= 2M give results < 2M
     pairs = ref.binary_cases(field, f.M2, closed)
     assert ((f.M2, f.M2) in pairs) == closed
     check_lazy("mul_lazy_dev", pairs, run(build, field, "F_MUL_LAZY", pairs),

@@ -1,5 +1,7 @@
 """A batch of Twist or Shout proofs over one SRS in one call (tns_twist_prove_batch,
-tns_shout_prove_batch and their _device forms; csrc/prove_batch.hip).  Every proof
+tns_shout_prove_batch and their _device forms; csrc/prove_batch.hip, with the transcripts of
+csrc/prove.hip zero_closure_transcript and the folds of csrc/zero_folds.hip fold_batch; DESIGN.md
+2.13).  Every proof
 of a batch must be byte for byte the proof the single prover returns for that row alone, pass the
 verifier, and for small traces equal the oracle's.  The route each call took, and forced routes and
 group splits, come from tests/device/provebatchprobe.hip, so a silent fall-back to the row loop

@@ -2,7 +2,9 @@
 the sizes the bench times it (2^20, 2^24) and between, against the C oracle's O(N)-per-round fold
 restatement (oracle/fastcpu.c fc_sumcheck_prove), which tests/test_fastcpu.py pins to the
 reference's closure algorithm (oracle.c orc_sumcheck_prove).  Round polynomials, challenges and
-the final evaluation must be bit-identical; host-buffer and device-resident entry points agree."""
+the final evaluation must be bit-identical; host-buffer and device-resident entry points agree.
+The compositions that no table enters (no terms; a constant alone: csrc/sumcheck.hip's host-only
+loop) are checked against the closure algorithm itself at small sizes."""
 import os
 
 import numpy as np
@@ -100,11 +102,79 @@ def test_generic_sumcheck_schedule_regimes(name, nv):
 @pytest.mark.parametrize("name", ["single", "pair2", "mixed", "cube4"])
 @pytest.mark.parametrize("nv", [3, 7, 9, 12])
 def test_generic_sumcheck_host_rounds(name, nv):
-    """The last rounds on the host (from the first round of <= 64 pairs, mle.hip SC_HOST_PAIRS)
+    """The last rounds on the host (from the first round of <= 64 pairs, sumcheck.hip SC_HOST_PAIRS)
     for one to four tables: at nv = 3 / 7 / 9 the device runs rounds 0-1 and the persistent tail's
     first round is the hand-over; at nv = 12 the tail runs rounds 2-4 first (512 .. 128 pairs) and
     the host takes rounds 5-11."""
     _regime(name, nv)
+
+
+def _closure_oracle(tabs, nv, claim, terms):
+    """The reference's closure algorithm itself (oracle.c orc_sumcheck_prove, O(N nv) per point:
+    small nv only): status, round polynomials, final evaluation, challenges."""
+    st, rounds, fin, chal = co.sumcheck_prove(tabs, nv, claim, terms)
+    return st, [co.fr_ints(r) for r in rounds], co.fr_ints(fin)[0], co.fr_ints(chal)
+
+
+@pytest.mark.parametrize("nv", [0, 1, 3, 6])
+def test_sumcheck_without_terms_matches_closure_oracle(nv):
+    """No terms: the composition is the empty sum, so every round polynomial is zero, the final
+    evaluation is zero and the transcript alone yields the challenges (the host-only loop of
+    sumcheck.hip); the tables take no part in the result."""
+    tabs = rand_tables(2, nv, seed=97 + nv)
+    st, rounds, fin, chal = _closure_oracle(tabs, nv, 0, [])
+    assert st == 0 and fin == 0 and rounds == [[0, 0, 0, 0]] * nv
+    proof, chals = ts.SumCheck(nv, 0).prove(tabs, [], ts.Transcript(bytes(32)), return_challenges=True)
+    assert proof.round_polynomials == rounds
+    assert proof.final_evaluation == 0
+    assert chals == chal
+    if nv in (1, 6):
+        ctx = ts.Context.get(0)
+        d = [ts.DeviceBuffer(ctx, t) for t in tabs]
+        p2, c2 = ts.SumCheck(nv, 0).prove_resident(d, [], ts.Transcript(bytes(32)))
+        assert p2 == proof and c2 == chal
+
+
+@pytest.mark.parametrize("nv", [0, 1, 3, 6])
+def test_sumcheck_without_terms_wrong_claim(nv):
+    """Claim 1 for the empty sum.  The oracle is the specification: with a round to run it fails
+    round 0's g(0) + g(1) check (src/sumcheck.rs:80-84) and so must the prover; at nv = 0 the
+    reference runs no round and checks nothing, so there both return the empty proof."""
+    tabs = rand_tables(2, nv, seed=97 + nv)
+    st, rounds, fin, chal = _closure_oracle(tabs, nv, 1, [])
+    assert (st != 0) == (nv > 0)
+    if st != 0:
+        with pytest.raises(ts.SumCheckError):
+            ts.SumCheck(nv, 1).prove(tabs, [], ts.Transcript(bytes(32)))
+        if nv in (1, 6):
+            d = [ts.DeviceBuffer(ts.Context.get(0), t) for t in tabs]
+            with pytest.raises(ts.SumCheckError):
+                ts.SumCheck(nv, 1).prove_resident(d, [], ts.Transcript(bytes(32)))
+    else:
+        proof, chals = ts.SumCheck(nv, 1).prove(tabs, [], ts.Transcript(bytes(32)), return_challenges=True)
+        assert (proof.round_polynomials, proof.final_evaluation, chals) == (rounds, fin, chal)
+
+
+@pytest.mark.parametrize("nv", [0, 1, 4])
+def test_sumcheck_constant_composition_matches_closure_oracle(nv):
+    """No tables, one constant term: every point of the cube contributes 5, the claim is 5 2^nv."""
+    terms = [(5, [])]
+    claim = 5 << nv
+    st, rounds, fin, chal = _closure_oracle([], nv, claim, terms)
+    assert st == 0 and fin == 5
+    proof, chals = ts.SumCheck(nv, claim).prove([], terms, ts.Transcript(bytes(32)), return_challenges=True)
+    assert proof.round_polynomials == rounds
+    assert proof.final_evaluation == fin
+    assert chals == chal
+    # a wrong claim: as above, the oracle decides (it checks nothing when there is no round)
+    st, rounds, fin, chal = _closure_oracle([], nv, claim + 1, terms)
+    assert (st != 0) == (nv > 0)
+    if st != 0:
+        with pytest.raises(ts.SumCheckError):
+            ts.SumCheck(nv, claim + 1).prove([], terms, ts.Transcript(bytes(32)))
+    else:
+        proof, chals = ts.SumCheck(nv, claim + 1).prove([], terms, ts.Transcript(bytes(32)), return_challenges=True)
+        assert (proof.round_polynomials, proof.final_evaluation, chals) == (rounds, fin, chal)
 
 
 def _regime(name, nv):

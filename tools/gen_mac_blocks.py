@@ -100,7 +100,7 @@ def gen_body(G, square=False, pair=False, redc=False):
     SHIFT = "  acc = (acc >> 32) | ((unsigned long long)c2 << 32);"
     # Dead carries, by the size of T = (the products) + m M, m < 2^256:
     #   canonical (mul_ps_dev, redc_dev):  T < M^2 + M 2^256
-    #   lazy (mul_lazy_dev, sqr_lazy_dev), inputs <= 2M (the closed domain of mle.hip included):
+    #   lazy (mul_lazy_dev, sqr_lazy_dev), inputs <= 2M (the closed domain of sumcheck.hip included):
     #                                      T <= 4M^2 + M 2^256
     #   pair (mul2_lazy_dev), inputs <= 2M: T <= 8M^2 + M 2^256
     # With M < 2^254 all of them are below 2^509 + 2^510 < 2^512.  The column sums add T up from
@@ -263,7 +263,7 @@ if __name__ == "__main__":
         f.write(gen(G_LIB, "mul_ps_dev") + "\n")
         f.write("// the same product without the final conditional subtraction: for inputs < 2M the\n"
                 "// result is < 2M (4M < 2^256), the lazy-reduction domain of the MSM accumulation; so do inputs\n"
-                "// <= 2M (4M^2 / R + M < 1.76 M: the closed domain of mle.hip's round kernel)\n")
+                "// <= 2M (4M^2 / R + M < 1.76 M: the closed domain of sumcheck.hip's round kernel)\n")
         f.write(gen(G_LIB, "mul_lazy_dev", reduce=False) + "\n")
         f.write("// the lazy product a * a: 36 products instead of 64 (input <= 2M < 2^255, see sqr_products;\n"
                 "// result < 2M as mul_lazy_dev's)\n")
@@ -308,7 +308,7 @@ def gen_reduce(suffix, K):
     # reduce_once: t = a - K; a = borrow ? a : t
     # t starts as the modulus (tied: no early-clobber output, see gen) and becomes a - K
     o.append("// a - M where a >= M: [0, 2M) -> [0, M)" if K == "M" else
-             "// a - 2M where a >= 2M: [0, 4M) -> [0, 2M); 4M itself -> 2M (the closed Fr domain of mle.hip)")
+             "// a - 2M where a >= 2M: [0, 4M) -> [0, 2M); 4M itself -> 2M (the closed Fr domain of sumcheck.hip)")
     o.append(f"template <class C>\n__device__ __forceinline__ void reduce_once{suffix}_dev(Fp<C> &a) {{\n  u32 t[8];\n"
              f"#pragma unroll\n  for (int i = 0; i < 8; i++) t[i] = C::{K}[i];")
     body = ["v_sub_co_u32_e32 %0, vcc, %8, %0"]
@@ -324,7 +324,7 @@ def gen_add(name_sfx, red_sfx):
     # add: r = a + b, then reduce_once (inputs < K: the sum < 2K < 2^256)
     # in place on r = a (tied: no early-clobber output, see gen)
     o.append("// a + b mod M: a, b in [0, M) -> [0, M)" if name_sfx == "" else
-             "// a + b in the lazy domain: a, b in [0, 2M) -> [0, 2M), = a + b mod M; a, b <= 2M -> <= 2M (mle.hip)")
+             "// a + b in the lazy domain: a, b in [0, 2M) -> [0, 2M), = a + b mod M; a, b <= 2M -> <= 2M (sumcheck.hip)")
     o.append(f"template <class C>\n__device__ __forceinline__ Fp<C> add{name_sfx}_dev(const Fp<C> &a, const Fp<C> &b) {{\n  Fp<C> r = a;")
     body = ["v_add_co_u32_e32 %0, vcc, %0, %8"]
     body += [f"v_addc_co_u32_e32 %{i}, vcc, %{i}, %{8 + i}, vcc" for i in range(1, 8)]
@@ -341,7 +341,7 @@ def gen_sub(name_sfx, K):
     # in place on r = a (tied); the borrow mask m and the masked modulus t are written only after the
     # last read of b, so they need no early clobber either (see gen)
     o.append("// a - b mod M: a, b in [0, M) -> [0, M)" if name_sfx == "" else
-             "// a - b in the lazy domain: a, b in [0, 2M) -> [0, 2M), = a - b mod M; a, b <= 2M -> <= 2M (mle.hip)")
+             "// a - b in the lazy domain: a, b in [0, 2M) -> [0, 2M), = a - b mod M; a, b <= 2M -> <= 2M (sumcheck.hip)")
     o.append(f"template <class C>\n__device__ __forceinline__ Fp<C> sub{name_sfx}_dev(const Fp<C> &a, const Fp<C> &b) {{\n  Fp<C> r = a;\n  u32 m, t[8];")
     body = ["v_sub_co_u32_e32 %0, vcc, %0, %17"]
     body += [f"v_subb_co_u32_e32 %{i}, vcc, %{i}, %{17 + i}, vcc" for i in range(1, 8)]

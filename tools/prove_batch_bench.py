@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the batched provers (tns_twist_prove_batch_device, tns_shout_prove_batch_device;
-csrc/prove_batch.hip) against the only route there was before -- a loop of tns_twist_prove_device /
+csrc/prove_batch.hip, folds in csrc/zero_folds.hip) against the only route there was before -- a loop of tns_twist_prove_device /
 tns_shout_prove_device over the same resident rows -- on one GPU: n_ops in 2^8 .. 2^14 x batch in
 {16, 256}.  Same process, the two interleaved, one warm-up each, the mean of --reps calls.  The
 loop is the yardstick: wherever the shipped rule (csrc/prove_batch_plan.hpp) takes the batched
