@@ -373,6 +373,39 @@ int tns_sumcheck_prove_device(tns_ctx *ctx, const uint64_t *const *d_tables, int
                               const uint64_t claimed_sum[4], const tns_term *terms, int n_terms,
                               tns_transcript *transcript, uint64_t *rounds_out, uint64_t final_out[4],
                               uint64_t *challenges_out);
+/* SumCheck::prove (src/sumcheck.rs:56-110) of `batch` independent instances of one shape in one call
+ * (DESIGN.md 2.14): one composition (terms, with the limits of tns_sumcheck_prove) over n_tables
+ * tables of 2^nv entries an instance.  tables[j]: batch x 2^nv Montgomery Fr, row-major (instance
+ * b's table j starts at b 2^nv), only read; claimed_sums: batch x 4 words; transcripts: batch
+ * distinct handles, each in whatever state its caller left it.  rounds_out: batch x nv x 4 Fr;
+ * finals_out: batch Fr; challenges_out: batch x nv Fr (nullable).  Instance b's rounds, final
+ * evaluation, challenges and transcript b's state on return are byte for byte what
+ * tns_sumcheck_prove_device gives for row b with transcript b alone.
+ * Route (csrc/sumcheck_batch_plan.hpp): the batched route is taken when batch >= 2, nv >= 1, some
+ * term has a table factor and 2^nv is below the measured crossover.  Then a group of instances
+ * advances in lockstep: one launch a round over every (instance, pair) of the group, the group's
+ * sums to the host in one copy, every instance's transcript turn, the group's challenges back in
+ * one copy -- nv + 1 launches a group whatever the batch.  The groups are the largest row counts
+ * whose fold scratch, 32 bytes x n_tables x rows x 0.75 x 2^nv in the context's workspaces, stays
+ * under 1 GiB; they run one after another.  Otherwise tns_sumcheck_prove_device runs row by row.
+ * Errors: a NULL handle or required array, the same transcript handle twice, n_tables outside 0..4,
+ * a term naming a missing table, more than 64 terms, batch * 2^nv above 2^32 ->
+ * TNS_ERR_INVALID_PARAMETERS; a failed device allocation -> TNS_ERR_OOM.  batch == 0 -> TNS_OK,
+ * nothing written.  An instance whose claim fails the g(0) + g(1) check (src/sumcheck.rs:80-84)
+ * fails the whole call with TNS_ERR_SUMCHECK; the message names the lowest failing instance of the
+ * earliest failing round ("Instance <b>: Round <r> consistency check failed").  An instance whose
+ * final value does not match its last claim (a device inconsistency) fails it likewise.  On error
+ * nothing the call queued is still running, the outputs and the transcripts are unspecified, and
+ * the context proves correctly afterwards. */
+int tns_sumcheck_prove_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
+                             const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
+                             tns_transcript *const *transcripts, uint64_t *rounds_out, uint64_t *finals_out,
+                             uint64_t *challenges_out);
+/* The same on tables already resident in HBM (tables[j] a device pointer, only read). */
+int tns_sumcheck_prove_batch_device(tns_ctx *ctx, const uint64_t *const *d_tables, int n_tables, unsigned nv,
+                                    size_t batch, const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
+                                    tns_transcript *const *transcripts, uint64_t *rounds_out, uint64_t *finals_out,
+                                    uint64_t *challenges_out);
 
 /* ---------------------------------------------------------------- protocols */
 /* Twist::prove (src/twist.rs:107-252).  The MemoryTrace's operations as SoA:

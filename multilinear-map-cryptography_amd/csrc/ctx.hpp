@@ -69,8 +69,8 @@ class SharedScratch {
   DevBuf slot[SCAN_LEVELS];
 };
 
-// The sum-check's workspaces.  The generic prover (sumcheck.hip: sumcheck_prove_dev,
-// composition_sum_dev) runs on Ctx::stream; the single zero-closure fold chain of Twist /
+// The sum-check's workspaces.  The generic provers (sumcheck.hip: sumcheck_prove_dev,
+// composition_sum_dev; sumcheck_batch.hip) run on Ctx::stream; the single zero-closure fold chain of Twist /
 // Shout::prove (zero_folds.hip: sumcheck_zero_folds_async) on Ctx::side.
 struct SumcheckWs {
   // second fold buffer per table (the input tables stay intact).  Both provers use it: the prove
@@ -90,6 +90,11 @@ struct SumcheckWs {
   DevBuf tail_sync;               // ... and relayed between the blocks of the persistent tail
   uint32_t chal_seq = 0;          // the flag value of the latest published challenge
   PinnedBuf host;                 // the zero-closure chain's challenges (in) and bound table values (out)
+  // the batched prover (sumcheck_batch.hip), on Ctx::stream, one group at a time:
+  DevBuf batch_fold[2];           // every table of every instance folded once (ping) and twice (pong)
+  DevBuf batch_state;             // per instance: the round's challenge, its four sums, the bound table values, the block counter
+  DevBuf batch_partials;          // the cross-block rounds' per-block sums
+  PinnedBuf batch_host;           // the group's sums and bound values (in) and challenges (out)
 };
 
 // The resident vectors of Twist / Shout::prove (prove.hip).  One proof runs at a time (the context

@@ -10,6 +10,7 @@ behaviour follow the reference:
 * ``KZGCommitment.commit/open``, ``KZGCommitmentValue.hash`` -- src/commitments.rs:73-199
 * ``MultilinearExtension``                          -- src/polynomials.rs:18-196
 * ``SumCheck.prove``                                -- src/sumcheck.rs:56-110
+* ``SumCheck.prove_batch``                          -- the same for a batch of instances in one call
 * ``Transcript``                                    -- src/utils.rs:134-204
 * ``poly_utils.lagrange_interpolate`` on nodes 0..n-1 -- src/polynomials.rs:301-352
 
@@ -1086,6 +1087,59 @@ class SumCheck:
         if raw:
             return rounds[:nv], fin, ch[:nv]
         return SumCheckProof([from_mont(r) for r in rounds[:nv]], from_mont(fin)[0]), (from_mont(ch[:nv]) if nv else [])
+
+    def _batch_call(self, fn, handle, ptrs, n_tables, terms, transcripts, claimed_sums, raw):
+        nv, batch = self.num_vars, len(transcripts)
+        if len(claimed_sums) != batch:
+            raise InvalidParameters("one claimed sum and one transcript per instance")
+        cl = to_mont([int(s) % R_MOD for s in claimed_sums]) if batch else np.zeros((1, 4), dtype=np.uint64)
+        trs = (C.c_void_p * max(1, batch))(*[t._h for t in transcripts])
+        rounds = np.zeros((max(1, batch), max(1, nv), 4, 4), dtype=np.uint64)
+        fin = np.zeros((max(1, batch), 4), dtype=np.uint64)
+        ch = np.zeros((max(1, batch), max(1, nv), 4), dtype=np.uint64)
+        # (the C arrays hold batch x nv rows back to back: views of exactly that shape when nv > 0)
+        rr = rounds if nv else rounds[:, :0]
+        cc = ch if nv else ch[:, :0]
+        _check(fn(handle, ptrs, n_tables, nv, batch, N.p64(cl), self._terms(terms), len(terms), trs,
+                  N.p64(rounds), N.p64(fin), N.p64(ch)))
+        if raw:
+            return rr[:batch], fin[:batch], cc[:batch]
+        proofs = [SumCheckProof([from_mont(r) for r in rr[b]], from_mont(fin[b])[0]) for b in range(batch)]
+        return proofs, [from_mont(cc[b]) if nv else [] for b in range(batch)]
+
+    def prove_batch(self, tables: Sequence[np.ndarray], terms: Sequence[Tuple[int, Sequence[int]]],
+                    transcripts: Sequence[Transcript], claimed_sums: Sequence[int], device: int = 0,
+                    return_challenges: bool = False):
+        """SumCheck::prove of len(transcripts) independent instances of num_vars variables under one
+        composition (tns_sumcheck_prove_batch): tables[j] holds every instance's table j, row-major
+        (batch x 2^num_vars Montgomery Fr), transcripts[b] and claimed_sums[b] belong to instance b
+        (this object's own claimed_sum takes no part).  Returns the list of SumCheckProof, each what
+        ``prove`` returns for that row on that transcript alone; with return_challenges also the
+        list of challenge lists."""
+        nv, batch = self.num_vars, len(transcripts)
+        arrs = [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1, 4) for t in tables]
+        for a in arrs:
+            if len(a) != batch << nv:
+                raise InvalidParameters("every table needs batch x 2^num_vars entries")
+        ptrs = (N.U64P * max(1, len(arrs)))(*[N.p64(_nonempty(a)) for a in arrs])
+        proofs, chals = self._batch_call(N.load().tns_sumcheck_prove_batch, Context.get(device).handle, ptrs, len(arrs),
+                                         terms, transcripts, claimed_sums, False)
+        return (proofs, chals) if return_challenges else proofs
+
+    def prove_batch_resident(self, tables: Sequence["DeviceBuffer"], terms: Sequence[Tuple[int, Sequence[int]]],
+                             transcripts: Sequence[Transcript], claimed_sums: Sequence[int], raw: bool = False):
+        """The same on tables already resident in HBM (DeviceBuffers of batch x 2^num_vars Montgomery
+        Fr, only read): (proofs, challenges) as ``prove_resident`` returns them, one of each per
+        instance.  raw=True returns the Montgomery arrays (rounds, finals, challenges)."""
+        nv, batch = self.num_vars, len(transcripts)
+        if not tables:
+            raise InvalidParameters("no tables")
+        for t in tables:
+            if t.nbytes != (32 * batch) << nv:
+                raise InvalidParameters("every table needs batch x 2^num_vars entries")
+        ptrs = (C.c_void_p * len(tables))(*[t.ptr for t in tables])
+        return self._batch_call(N.load().tns_sumcheck_prove_batch_device, tables[0].ctx.handle, ptrs, len(tables), terms,
+                                transcripts, claimed_sums, raw)
 
 
 # ----------------------------------------------------------------------------- Twist

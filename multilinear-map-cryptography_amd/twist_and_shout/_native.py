@@ -132,6 +132,12 @@ SIGNATURES = [
     ("tns_sumcheck_prove_device", C.c_int,
      [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint, U64P, C.POINTER(TnsTerm), C.c_int, C.c_void_p, U64P,
       U64P, U64P]),
+    ("tns_sumcheck_prove_batch", C.c_int,
+     [C.c_void_p, C.POINTER(U64P), C.c_int, C.c_uint, C.c_size_t, U64P, C.POINTER(TnsTerm), C.c_int,
+      C.POINTER(C.c_void_p), U64P, U64P, U64P]),
+    ("tns_sumcheck_prove_batch_device", C.c_int,
+     [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint, C.c_size_t, U64P, C.POINTER(TnsTerm), C.c_int,
+      C.POINTER(C.c_void_p), U64P, U64P, U64P]),
     ("tns_twist_prove", C.c_int,
      [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), U64P, U64P, U8P, C.c_size_t, C.POINTER(TnsProof)]),
     ("tns_shout_prove", C.c_int,
