@@ -345,6 +345,27 @@ int tns_mle_evaluate(tns_ctx *ctx, const uint64_t *evals, size_t n_evals, unsign
  * first k (least-significant) variables; out has 2^(nv-k) entries.  evals as above. */
 int tns_mle_partial_evaluate(tns_ctx *ctx, const uint64_t *evals, size_t n_evals, unsigned nv,
                              const uint64_t *fixed, unsigned k, uint64_t *out);
+/* MultilinearExtension::evaluate (src/polynomials.rs:85-122) on a table of exactly 2^nv Montgomery
+ * Fr already resident in HBM (a device pointer, only read), in one pass: the same
+ * value tns_mle_evaluate returns for these entries. */
+int tns_mle_evaluate_device(tns_ctx *ctx, const uint64_t *d_evals, unsigned nv, const uint64_t *point,
+                            uint64_t out[4]);
+/* MultilinearExtension::evaluate (src/polynomials.rs:85-122) of `batch` instances of n_tables <= 4
+ * tables each, every instance at a point of its own, in one pass:
+ *   values_out[b n_tables + j] = sum_x tables[j][b 2^nv + x] prod_i (x_i ? points[b nv + i] : 1 - points[b nv + i])
+ * with variable i <-> index bit i, least significant first.  tables[j]: batch x 2^nv Montgomery
+ * Fr, row-major, only read -- the layout of tns_sumcheck_prove_batch; points: batch x nv Fr;
+ * values_out: batch x n_tables Fr, canonical Montgomery forms.  Every entry is read once; the
+ * device scratch is at most 1/128 of the tables' bytes plus a few words an instance; at most two
+ * launches (one when nv <= 8) whatever nv and batch, one copy in, one copy out, one synchronise.
+ * Errors: a NULL handle or required array, n_tables outside 0..4, nv above 30, batch * 2^nv above
+ * 2^32 -> TNS_ERR_INVALID_PARAMETERS; a failed device allocation -> TNS_ERR_OOM.  batch == 0 or
+ * n_tables == 0 -> TNS_OK, nothing written. */
+int tns_mle_evaluate_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
+                           const uint64_t *points, uint64_t *values_out);
+/* The same on tables already resident in HBM (tables[j] a device pointer, only read). */
+int tns_mle_evaluate_batch_device(tns_ctx *ctx, const uint64_t *const *d_tables, int n_tables, unsigned nv,
+                                  size_t batch, const uint64_t *points, uint64_t *values_out);
 
 /* ---------------------------------------------------------------- transcript (src/utils.rs:134-204) */
 tns_transcript *tns_transcript_new(const uint8_t seed[32]);
@@ -406,6 +427,46 @@ int tns_sumcheck_prove_batch_device(tns_ctx *ctx, const uint64_t *const *d_table
                                     size_t batch, const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
                                     tns_transcript *const *transcripts, uint64_t *rounds_out, uint64_t *finals_out,
                                     uint64_t *challenges_out);
+/* SumCheck::verify (src/sumcheck.rs:113-153) for any claimed sum, on the host.  rounds: n_rounds x 4
+ * Fr (tns_sumcheck_prove's rounds_out).  n_rounds != nv -> TNS_ERR_SUMCHECK ("Proof has wrong number
+ * of rounds"), the transcript untouched.  Otherwise the reference's loop: a round whose g(0) + g(1)
+ * differs from the running claim stops the replay before that round is appended -- *ok = 0,
+ * *n_challenges_out = that round's index, the transcript holds the earlier rounds only; when the
+ * replay runs through, *ok = (last claim == final_eval) and *n_challenges_out = nv.  An invalid proof
+ * is a result, not an error: TNS_OK.  challenges_out: nv Fr (nullable), the first *n_challenges_out
+ * written; n_challenges_out nullable.  The transcript's bytes after a replay that ran through are
+ * the ones tns_sumcheck_prove leaves.  Like the reference, this compares final_eval with a number
+ * the proof itself determines; tns_sumcheck_verify_batch checks it against the tables. */
+int tns_sumcheck_verify(unsigned nv, const uint64_t claimed_sum[4], const uint64_t *rounds, size_t n_rounds,
+                        const uint64_t final_eval[4], tns_transcript *transcript, uint64_t *challenges_out,
+                        size_t *n_challenges_out, int *ok);
+/* SumCheck::verify (src/sumcheck.rs:113-153) of `batch` proofs of one shape, each on its own
+ * transcript, and -- when tables != NULL -- the check the reference leaves to its caller: the final
+ * evaluation against the composition of the tables' multilinear extensions at the challenge point
+ * (MultilinearExtension::evaluate, src/polynomials.rs:85-122).  tables, terms, claimed_sums,
+ * transcripts as tns_sumcheck_prove_batch; rounds: batch x nv x 4 Fr; finals: batch Fr.
+ * verdicts_out[b]: 0 valid; 1 a round check failed (n_challenges_out[b] = its index); 2 the last
+ * claim differs from the final evaluation; 3 the final evaluation differs from
+ * sum_t coeff_t prod_j value[j] at instance b's challenges (tables != NULL only).
+ * The host replays every instance (tns_sumcheck_verify's loop), then ONE tns_mle_evaluate_batch pass
+ * runs over the whole batch at the challenge points -- instances at verdict 1 or 2 ride along at the
+ * zero point and their values_out rows are zero -- then the host evaluates the composition per
+ * instance.  challenges_out: batch x nv Fr (nullable), entries past n_challenges_out[b] zero;
+ * n_challenges_out: batch words (nullable); values_out: batch x n_tables Fr (nullable, untouched
+ * when tables == NULL).  nv == 0: no rounds, verdict 2 iff claim != final, the table value is
+ * tables[j][b].  Errors as tns_sumcheck_prove_batch (an invalid proof is a verdict, not an error);
+ * batch == 0 -> TNS_OK, nothing written. */
+int tns_sumcheck_verify_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
+                              const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
+                              tns_transcript *const *transcripts, const uint64_t *rounds, const uint64_t *finals,
+                              uint64_t *challenges_out, uint32_t *n_challenges_out, int *verdicts_out,
+                              uint64_t *values_out);
+/* The same on tables already resident in HBM (tables[j] a device pointer, only read). */
+int tns_sumcheck_verify_batch_device(tns_ctx *ctx, const uint64_t *const *d_tables, int n_tables, unsigned nv,
+                                     size_t batch, const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
+                                     tns_transcript *const *transcripts, const uint64_t *rounds,
+                                     const uint64_t *finals, uint64_t *challenges_out, uint32_t *n_challenges_out,
+                                     int *verdicts_out, uint64_t *values_out);
 
 /* ---------------------------------------------------------------- protocols */
 /* Twist::prove (src/twist.rs:107-252).  The MemoryTrace's operations as SoA:

@@ -149,6 +149,18 @@ int sumcheck_prove_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tabl
                          const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
                          tns_transcript *const *transcripts, uint64_t *rounds_out, uint64_t *finals_out,
                          uint64_t *challenges_out, bool resident, const ScBatchLimits &lim, ScBatchReport *rep);
+// mle_eval.hip: tns_mle_evaluate_batch(_device) with the launch limits as an argument (the entry
+// points pass the defaults, the probe of tests/device/mleevalprobe.hip forces them); rep
+// (optional): the regime, the launches, the blocks and the rows a thread took
+int mle_evaluate_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
+                       const uint64_t *points, uint64_t *values_out, bool resident, const MleEvalLimits &lim,
+                       MleEvalReport *rep);
+// sumcheck_verify.hip: tns_sumcheck_verify_batch(_device) likewise; rep: the one evaluation pass
+int sumcheck_verify_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
+                          const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
+                          tns_transcript *const *transcripts, const uint64_t *rounds, const uint64_t *finals,
+                          uint64_t *challenges_out, uint32_t *n_challenges_out, int *verdicts_out, uint64_t *values_out,
+                          bool resident, const MleEvalLimits &lim, MleEvalReport *rep);
 // abi_host.cpp: a tns_vk's three points, each checked against its curve
 struct Vk {
   G1Affine g1;

@@ -170,6 +170,26 @@ int tns_shout_verify(const tns_vk *vk, const tns_proof *proof, int *ok) {
   return verify_proof(vk, proof, "table_commitment", "index_commitment", ok);
 }
 
+// SumCheck::verify (src/sumcheck.rs:113-153)
+int tns_sumcheck_verify(unsigned nv, const uint64_t claimed_sum[4], const uint64_t *rounds, size_t n_rounds,
+                        const uint64_t final_eval[4], tns_transcript *transcript, uint64_t *challenges_out,
+                        size_t *n_challenges_out, int *ok) {
+  return guarded([&]() {
+    if (!claimed_sum || !final_eval || !transcript || !ok || (n_rounds > 0 && !rounds))
+      throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
+    if (n_rounds != nv) throw Error(TNS_ERR_SUMCHECK, "Proof has wrong number of rounds");  // :118-122
+    std::vector<Fr> rd(4 * (size_t)nv + 1), chal((size_t)nv + 1);
+    if (nv) std::memcpy((void *)rd.data(), rounds, sizeof(Fr) * 4 * (size_t)nv);
+    unsigned nc = 0;
+    const int v = sumcheck_replay_host(transcript->t, fr_load(claimed_sum), rd.data(), nv, fr_load(final_eval),
+                                       chal.data(), &nc);
+    if (challenges_out && nc) std::memcpy(challenges_out, chal.data(), sizeof(Fr) * nc);
+    if (n_challenges_out) *n_challenges_out = nc;
+    *ok = v == 0 ? 1 : 0;
+    return TNS_OK;
+  });
+}
+
 int tns_pairing(const uint64_t g1_affine[8], const uint64_t g2_affine[16], uint64_t out[48]) {
   return guarded([&]() {
     Fq e[12];

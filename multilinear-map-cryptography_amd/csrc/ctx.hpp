@@ -97,6 +97,16 @@ struct SumcheckWs {
   PinnedBuf batch_host;           // the group's sums and bound values (in) and challenges (out)
 };
 
+// The one-pass batched MLE evaluation (mle_eval.hip), on Ctx::stream, one call at a time (the
+// context lock).  Together at most 1/128 of the tables' bytes plus a few words an instance.
+struct MleEvalWs {
+  DevBuf points;    // the call's points, batch x nv
+  DevBuf eq_hi;     // per instance the eq table of the variables above the low 8: 2^(nv-8) entries
+  DevBuf partials;  // the cross-block regime's per-block sums, n_tables a block
+  DevBuf values;    // the results, batch x n_tables
+  DevBuf counters;  // per instance the blocks that have finished; zero between calls
+};
+
 // The resident vectors of Twist / Shout::prove (prove.hip).  One proof runs at a time (the context
 // lock), and both protocols use the same names: Twist's addresses and values are Shout's table and
 // lookup indices.
@@ -120,6 +130,7 @@ struct Ctx {
   DevBuf interp_x2;                     // interpolation's working vector of 2n elements (interp.hip)
   DevBuf sweep_totals;                  // the node sweep's per-block totals (lagrange.hip)
   SumcheckWs sc;
+  MleEvalWs mle_eval;
   MappedHostBuf inv_mapped;             // the batch inversion's grand product + flag (lagrange.hip)
   uint32_t inv_seq = 0;
   hipStream_t side = nullptr;  // the zero-closure folds
@@ -216,6 +227,28 @@ struct CtxScope {
 // mle.hip
 void mle_fold_dev(Ctx *c, const Fr *in, Fr *out, size_t half, const Fr &r);
 Fr mle_evaluate_dev(Ctx *c, const Fr *evals, unsigned nv, const Fr *point_host);
+
+// mle_eval.hip
+// values_host[b k + j] = MLE(tables[j] + b 2^nv)(points_host + b nv) for every instance b and table
+// j < k <= 4 in one pass: every entry read once, at most two launches whatever nv and batch, one
+// synchronise.  lim: the launch geometry's limits (the entry points pass the defaults, the probe
+// of tests/device/mleevalprobe.hip forces them); rep (optional): what ran.
+enum : int { MLE_EVAL_NONE = 0, MLE_EVAL_WAVE = 1, MLE_EVAL_BLOCK = 2, MLE_EVAL_BLOCKS = 3 };
+struct MleEvalLimits {
+  // a thread takes more rows only while the launch keeps this many blocks, and at most
+  // 2^max_log_rows.  Measured (profiles/mle_eval_bench.json rows_sweep): a block's
+  // fixed cost -- the eq_lo products, the block sum and, across blocks, the fence before its
+  // counter increment -- outweighs what more blocks a CU hide, so one block a CU (256 CUs) is the
+  // floor; beyond 64 rows a thread the time is flat
+  size_t min_blocks = 256;
+  unsigned max_log_rows = 6;
+};
+struct MleEvalReport {
+  int regime = MLE_EVAL_NONE;     // how an instance's sum is formed: part of a wave, one block, several blocks
+  size_t launches = 0, blocks = 0, rows_per_thread = 0;  // blocks: of the dot-product launch
+};
+void mle_evaluate_batch_dev(Ctx *c, const Fr *const *tables, int k, unsigned nv, size_t batch, const Fr *points_host,
+                            Fr *values_host, const MleEvalLimits &lim = MleEvalLimits(), MleEvalReport *rep = nullptr);
 
 // sumcheck.hip
 struct SumcheckTerm {

@@ -33,6 +33,16 @@ bool kzg_batch_verify_host(const G1Affine &g1, const G2Affine &g2, const G2Affin
                            const G1Affine *C, const Fr *z, const Fr *v, const G1Affine *pi);
 // the batched check's challenges [first, first + count) of `seed`, canonical 4 x u64 each
 void verify_challenges_host(const uint8_t seed[32], uint64_t first, size_t count, uint64_t *out);
+struct HostTranscript;
+// SumCheck::verify's replay (src/sumcheck.rs:124-152) for any claimed sum.  Returns 0: every round
+// check held and the last claim equals final_eval; 1: round *n_chal failed g(0) + g(1) == claim --
+// the replay stopped before appending it, the transcript holds the earlier rounds only; 2: the
+// rounds held, the last claim differs.  chal (optional, nv entries): the challenges drawn,
+// *n_chal (optional) of them.
+int sumcheck_replay_host(HostTranscript &tr, const Fr &claimed, const Fr *rounds, unsigned nv, const Fr &final_eval,
+                         Fr *chal, unsigned *n_chal);
+// ... with claimed sum 0, as Twist::verify / Shout::verify call it
+bool sumcheck_verify_host(HostTranscript &tr, const Fr *rounds, unsigned nv, const Fr &final_eval);
 bool protocol_verify_host(const G1Affine &g1, const G2Affine &g2, const G2Affine &g2_tau, const char *label0,
                           const char *label1, const G1Affine C[2], const Fr *rounds, unsigned nv,
                           const Fr &final_eval, unsigned n_openings, const G1Affine pi[2], const Fr vals[2]);

@@ -914,6 +914,27 @@ class poly_utils:  # noqa: N801  (mirrors the Rust module name)
         return acc
 
 
+def _points_mont(points, raw: bool) -> Tuple[np.ndarray, int, int]:
+    """batch rows of num_vars coordinates as one Montgomery array: (array, batch, num_vars)"""
+    if raw:
+        pts = np.ascontiguousarray(points, dtype=np.uint64)
+        if pts.ndim != 3 or pts.shape[2] != 4:
+            raise InvalidParameters("raw points are a batch x num_vars x 4 array")
+        return _nonempty(pts.reshape(-1, 4)), pts.shape[0], pts.shape[1]
+    rows = [list(p) for p in points]
+    nv = len(rows[0]) if rows else 0
+    if any(len(r) != nv for r in rows):
+        raise InvalidParameters("every point needs num_vars coordinates")
+    flat = [int(x) % R_MOD for r in rows for x in r]
+    return _nonempty(to_mont(flat) if flat else np.zeros((0, 4), dtype=np.uint64)), len(rows), nv
+
+
+def _values_out(out: np.ndarray, batch: int, k: int, raw: bool):
+    if raw:
+        return out[:batch, :k]
+    return [from_mont(out[b, :k]) if k else [] for b in range(batch)]
+
+
 class MultilinearExtension:
     """src/polynomials.rs:18-196 -- evaluate / partial_evaluate run on the GPU (fold kernels)."""
 
@@ -974,6 +995,24 @@ class MultilinearExtension:
         _check(N.load().tns_mle_evaluate(Context.get(device).handle, N.p64(ev), min(len(self.evaluations), 1 << self.num_vars),
                                          self.num_vars, N.p64(pt), N.p64(out)))
         return from_mont(out)[0]
+
+    @staticmethod
+    def evaluate_batch(tables: Sequence[np.ndarray], points, device: int = 0, raw: bool = False):  # :85-122
+        """Every instance's tables at the instance's own point in one pass (tns_mle_evaluate_batch):
+        tables[j] holds every instance's table j, row-major (batch x 2^num_vars Montgomery Fr, the
+        layout of ``SumCheck.prove_batch``); points is batch rows of num_vars integers (raw=True: a
+        batch x num_vars x 4 Montgomery array).  Returns per instance the list of its tables'
+        values (raw=True: the batch x len(tables) x 4 Montgomery array)."""
+        pts, batch, nv = _points_mont(points, raw)
+        arrs = [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1, 4) for t in tables]
+        for a in arrs:
+            if len(a) != batch << nv:
+                raise InvalidParameters("every table needs batch x 2^num_vars entries")
+        ptrs = (N.U64P * max(1, len(arrs)))(*[N.p64(_nonempty(a)) for a in arrs])
+        out = np.zeros((max(1, batch), max(1, len(arrs)), 4), dtype=np.uint64)
+        _check(N.load().tns_mle_evaluate_batch(Context.get(device).handle, ptrs, len(arrs), nv, batch, N.p64(pts),
+                                               N.p64(out)))
+        return _values_out(out, batch, len(arrs), raw)
 
     def partial_evaluate(self, fixed: Sequence[int], device: int = 0) -> "MultilinearExtension":  # :126-161
         k = len(fixed)
@@ -1140,6 +1179,119 @@ class SumCheck:
         ptrs = (C.c_void_p * len(tables))(*[t.ptr for t in tables])
         return self._batch_call(N.load().tns_sumcheck_prove_batch_device, tables[0].ctx.handle, ptrs, len(tables), terms,
                                 transcripts, claimed_sums, raw)
+
+    @staticmethod
+    def _round_rows(proof: "SumCheckProof") -> np.ndarray:
+        rows = []
+        for g in proof.round_polynomials:
+            if len(g) > 4:
+                raise InvalidParameters("a round polynomial has at most 4 coefficients")
+            rows.extend(list(g) + [0] * (4 - len(g)))
+        return to_mont(rows).reshape(-1, 4, 4) if rows else np.zeros((0, 4, 4), dtype=np.uint64)
+
+    def verify(self, proof: "SumCheckProof", transcript: Transcript) -> Tuple[bool, List[int]]:
+        """SumCheck::verify (src/sumcheck.rs:113-153) on the host: (ok, the challenges drawn).  A
+        round whose g(0) + g(1) differs from the running claim returns (False, the challenges before
+        it) and leaves the transcript at the earlier rounds; a wrong number of rounds raises
+        SumCheckError.  Like the reference this compares ``final_evaluation`` with the last claim
+        alone; ``verify_tables`` also checks it against the tables."""
+        nv = self.num_vars
+        rounds = self._round_rows(proof)
+        cl = to_mont([self.claimed_sum])[0]
+        fin = to_mont([proof.final_evaluation])[0]
+        ch = np.zeros((max(1, nv), 4), dtype=np.uint64)
+        nch = C.c_size_t(0)
+        ok = C.c_int(0)
+        _check(N.load().tns_sumcheck_verify(nv, N.p64(cl), N.p64(_nonempty(rounds.reshape(-1, 4))), len(rounds), N.p64(fin),
+                                            transcript._h, N.p64(ch), C.byref(nch), C.byref(ok)))
+        return bool(ok.value), (from_mont(ch[:nch.value]) if nch.value else [])
+
+    def verify_tables(self, proof: "SumCheckProof", tables: Sequence[Sequence[int]],
+                      terms: Sequence[Tuple[int, Sequence[int]]], transcript: Transcript,
+                      device: int = 0) -> Tuple[bool, List[int]]:
+        """``verify``, and the final evaluation against the composition of the tables' multilinear
+        extensions at the challenges (one evaluation pass on the GPU): (ok, challenges)."""
+        arrs = [np.ascontiguousarray(t if isinstance(t, np.ndarray) else to_mont(list(t)), dtype=np.uint64)
+                for t in tables]
+        verdicts, chals = self.verify_batch([proof], arrs, terms, [transcript], [self.claimed_sum], device=device)
+        return verdicts[0] == 0, chals[0]
+
+    def _verify_batch_call(self, fn, handle, ptrs, n_tables, terms, transcripts, claimed_sums, proofs, raw,
+                           return_values):
+        nv, batch = self.num_vars, len(transcripts)
+        if len(claimed_sums) != batch:
+            raise InvalidParameters("one claimed sum and one transcript per instance")
+        if isinstance(proofs, tuple):  # (rounds, finals) as prove_batch_resident(raw=True) returns them
+            rounds = np.ascontiguousarray(proofs[0], dtype=np.uint64).reshape(-1, 4)
+            fin = np.ascontiguousarray(proofs[1], dtype=np.uint64).reshape(-1, 4)
+        else:
+            for p in proofs:
+                if len(p.round_polynomials) != nv:
+                    raise SumCheckError("Proof has wrong number of rounds")
+            rounds = (np.concatenate([self._round_rows(p) for p in proofs]).reshape(-1, 4) if batch and nv
+                      else np.zeros((0, 4), dtype=np.uint64))
+            fin = to_mont([p.final_evaluation for p in proofs]) if batch else np.zeros((0, 4), dtype=np.uint64)
+        if len(rounds) != 4 * nv * batch or len(fin) != batch:
+            raise InvalidParameters("one proof of num_vars rounds per instance")
+        cl = to_mont([int(s) % R_MOD for s in claimed_sums]) if batch else np.zeros((1, 4), dtype=np.uint64)
+        trs = (C.c_void_p * max(1, batch))(*[t._h for t in transcripts])
+        ch = np.zeros((max(1, batch), max(1, nv), 4), dtype=np.uint64)
+        nch = np.zeros(max(1, batch), dtype=np.uint32)
+        verdicts = np.zeros(max(1, batch), dtype=np.int32)
+        k = max(n_tables, 0)
+        vals = np.zeros((max(1, batch), max(1, k), 4), dtype=np.uint64)
+        _check(fn(handle, ptrs, n_tables, nv, batch, N.p64(cl), self._terms(terms), len(terms), trs,
+                  N.p64(_nonempty(rounds)), N.p64(_nonempty(fin)), N.p64(ch), nch.ctypes.data_as(C.POINTER(C.c_uint32)),
+                  verdicts.ctypes.data_as(C.POINTER(C.c_int)), N.p64(vals) if ptrs is not None else None))
+        cc = ch if nv else ch[:, :0]
+        if raw:
+            out = (verdicts[:batch], cc[:batch], nch[:batch])
+            return out + (vals[:batch, :k],) if return_values else out
+        chals = [from_mont(cc[b, :int(nch[b])]) if nch[b] else [] for b in range(batch)]
+        out = ([int(v) for v in verdicts[:batch]], chals)
+        return out + (_values_out(vals, batch, k, False),) if return_values else out
+
+    def verify_batch(self, proofs, tables: Optional[Sequence[np.ndarray]], terms: Sequence[Tuple[int, Sequence[int]]],
+                     transcripts: Sequence[Transcript], claimed_sums: Sequence[int], device: int = 0,
+                     raw: bool = False, return_values: bool = False):
+        """SumCheck::verify of len(transcripts) proofs of num_vars variables under one composition,
+        each on its own transcript (tns_sumcheck_verify_batch); tables, terms, transcripts and
+        claimed_sums as ``prove_batch``, proofs a list of SumCheckProof (or the Montgomery arrays
+        (rounds, finals)).  With tables, every final evaluation is also checked against the
+        composition of the tables' multilinear extensions at the instance's challenges, in one
+        evaluation pass over the whole batch; tables=None is the reference's check alone.
+        Returns (verdicts, challenges): verdict 0 valid, 1 a round check failed (the challenges stop
+        before it), 2 the last claim differs from the final evaluation, 3 the final evaluation
+        differs from the tables' value.  return_values adds the tables' values per instance (zero
+        rows at verdicts 1 and 2); raw=True returns arrays (verdicts, challenges, n_challenges[,
+        values]) in Montgomery form."""
+        nv, batch = self.num_vars, len(transcripts)
+        if tables is None:
+            return self._verify_batch_call(N.load().tns_sumcheck_verify_batch, Context.get(device).handle, None,
+                                           1 + max([max(ix) for _, ix in terms if len(ix)], default=-1), terms,
+                                           transcripts, claimed_sums, proofs, raw, return_values)
+        arrs = [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1, 4) for t in tables]
+        for a in arrs:
+            if len(a) != batch << nv:
+                raise InvalidParameters("every table needs batch x 2^num_vars entries")
+        ptrs = (N.U64P * max(1, len(arrs)))(*[N.p64(_nonempty(a)) for a in arrs])
+        return self._verify_batch_call(N.load().tns_sumcheck_verify_batch, Context.get(device).handle, ptrs, len(arrs),
+                                       terms, transcripts, claimed_sums, proofs, raw, return_values)
+
+    def verify_batch_resident(self, proofs, tables: Sequence["DeviceBuffer"], terms: Sequence[Tuple[int, Sequence[int]]],
+                              transcripts: Sequence[Transcript], claimed_sums: Sequence[int], raw: bool = False,
+                              return_values: bool = False):
+        """``verify_batch`` on tables already resident in HBM (DeviceBuffers of batch x 2^num_vars
+        Montgomery Fr, only read)."""
+        nv, batch = self.num_vars, len(transcripts)
+        if not tables:
+            raise InvalidParameters("no tables")
+        for t in tables:
+            if t.nbytes != (32 * batch) << nv:
+                raise InvalidParameters("every table needs batch x 2^num_vars entries")
+        ptrs = (C.c_void_p * len(tables))(*[t.ptr for t in tables])
+        return self._verify_batch_call(N.load().tns_sumcheck_verify_batch_device, tables[0].ctx.handle, ptrs, len(tables),
+                                       terms, transcripts, claimed_sums, proofs, raw, return_values)
 
 
 # ----------------------------------------------------------------------------- Twist
@@ -1577,6 +1729,35 @@ def buffer_download(buf: DeviceBuffer, out: np.ndarray):
     """Copy the buffer's first out.nbytes bytes into the (C-contiguous) host array out."""
     assert out.flags["C_CONTIGUOUS"]
     _check(N.load().tns_buffer_download(buf.handle, out.ctypes.data_as(C.c_void_p), out.nbytes))
+
+
+def mle_evaluate_resident(buf: DeviceBuffer, num_vars: int, point: Sequence[int]) -> int:
+    """MultilinearExtension::evaluate of a resident table of exactly 2^num_vars Montgomery Fr (only
+    read) in one pass (tns_mle_evaluate_device)."""
+    if len(point) != num_vars:
+        raise AssertionError("Point dimension must match number of variables")
+    if buf.nbytes != 32 << num_vars:
+        raise InvalidParameters("the table needs 2^num_vars entries")
+    pt = _nonempty(to_mont(list(point)) if num_vars else np.zeros((0, 4), dtype=np.uint64))
+    out = np.zeros(4, dtype=np.uint64)
+    _check(N.load().tns_mle_evaluate_device(buf.ctx.handle, buf.ptr, num_vars, N.p64(pt), N.p64(out)))
+    return from_mont(out)[0]
+
+
+def mle_evaluate_batch_resident(tables: Sequence[DeviceBuffer], points, raw: bool = False):
+    """``MultilinearExtension.evaluate_batch`` on tables already resident in HBM (DeviceBuffers of
+    batch x 2^num_vars Montgomery Fr, only read): tns_mle_evaluate_batch_device."""
+    pts, batch, nv = _points_mont(points, raw)
+    if not tables:
+        raise InvalidParameters("no tables")
+    for t in tables:
+        if t.nbytes != (32 * batch) << nv:
+            raise InvalidParameters("every table needs batch x 2^num_vars entries")
+    ptrs = (C.c_void_p * len(tables))(*[t.ptr for t in tables])
+    out = np.zeros((max(1, batch), len(tables), 4), dtype=np.uint64)
+    _check(N.load().tns_mle_evaluate_batch_device(tables[0].ctx.handle, ptrs, len(tables), nv, batch, N.p64(pts),
+                                                  N.p64(out)))
+    return _values_out(out, batch, len(tables), raw)
 
 
 def twist_prove_resident(pp: ProverParams, addr: DeviceBuffer, value: DeviceBuffer, is_write: DeviceBuffer,

@@ -119,6 +119,10 @@ SIGNATURES = [
     ("tns_interpolate_consecutive", C.c_int, [C.c_void_p, U64P, C.c_size_t, U64P]),
     ("tns_mle_evaluate", C.c_int, [C.c_void_p, U64P, C.c_size_t, C.c_uint, U64P, U64P]),
     ("tns_mle_partial_evaluate", C.c_int, [C.c_void_p, U64P, C.c_size_t, C.c_uint, U64P, C.c_uint, U64P]),
+    ("tns_mle_evaluate_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, U64P, U64P]),
+    ("tns_mle_evaluate_batch", C.c_int, [C.c_void_p, C.POINTER(U64P), C.c_int, C.c_uint, C.c_size_t, U64P, U64P]),
+    ("tns_mle_evaluate_batch_device", C.c_int,
+     [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint, C.c_size_t, U64P, U64P]),
     ("tns_transcript_new", C.c_void_p, [U8P]),
     ("tns_transcript_free", None, [C.c_void_p]),
     ("tns_transcript_append_field_element", None, [C.c_void_p, U8P, C.c_size_t, U64P]),
@@ -138,6 +142,14 @@ SIGNATURES = [
     ("tns_sumcheck_prove_batch_device", C.c_int,
      [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint, C.c_size_t, U64P, C.POINTER(TnsTerm), C.c_int,
       C.POINTER(C.c_void_p), U64P, U64P, U64P]),
+    ("tns_sumcheck_verify", C.c_int,
+     [C.c_uint, U64P, U64P, C.c_size_t, U64P, C.c_void_p, U64P, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    ("tns_sumcheck_verify_batch", C.c_int,
+     [C.c_void_p, C.POINTER(U64P), C.c_int, C.c_uint, C.c_size_t, U64P, C.POINTER(TnsTerm), C.c_int,
+      C.POINTER(C.c_void_p), U64P, U64P, U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_int), U64P]),
+    ("tns_sumcheck_verify_batch_device", C.c_int,
+     [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint, C.c_size_t, U64P, C.POINTER(TnsTerm), C.c_int,
+      C.POINTER(C.c_void_p), U64P, U64P, U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_int), U64P]),
     ("tns_twist_prove", C.c_int,
      [C.c_void_p, C.c_void_p, C.POINTER(TnsParams), U64P, U64P, U8P, C.c_size_t, C.POINTER(TnsProof)]),
     ("tns_shout_prove", C.c_int,
