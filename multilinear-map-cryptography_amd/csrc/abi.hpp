@@ -1,6 +1,7 @@
-// abi.hpp -- what the translation units of the C ABI (api.hip, kzg.hip, kzg_batch.hip, prove.hip,
-// prove_batch.hip, abi_host.cpp) share: the opaque handle types of include/tns.h, the error guard of every entry point, and the
-// KZG routes of kzg.hip.
+// abi.hpp -- what the translation units of the C ABI share: the opaque handle types of
+// include/tns.h, the error guard of every entry point, the KZG routes of kzg.hip and kzg_batch.hip,
+// and the batched provers' and verifiers' internal entry points.  (The generic sum-check family
+// declares its own in sumcheck.hpp.)
 #pragma once
 #include <chrono>
 #include <cstring>
@@ -11,7 +12,6 @@
 #include "ctx.hpp"
 #include "host.hpp"
 #include "srs.hpp"
-#include "sumcheck_batch_plan.hpp"
 
 struct tns_ctx {
   tns::Ctx c;
@@ -137,30 +137,6 @@ int twist_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params
 int shout_prove_batch(tns_ctx *ctx, const tns_srs *srs, const tns_params *params, const uint64_t *entries,
                       size_t n_entries, const uint64_t *indices, size_t n_lookups, size_t batch, tns_proof *out,
                       bool resident, const BatchLimits &lim, ProveBatchReport *rep);
-// sumcheck_batch.hip: tns_sumcheck_prove_batch(_device) with the limits as an argument (the entry
-// points pass the defaults, the probe of tests/device/scbatchprobe.hip forces routes and splits);
-// rep (optional): what the call took -- the plan's route and groups, and the launches the batched
-// route queued (nv + 1 a group; 0 on the rows route)
-struct ScBatchReport {
-  int route = BATCH_ROUTE_ROWS;
-  size_t group_rows = 1, groups = 0, launches = 0;
-};
-int sumcheck_prove_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
-                         const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
-                         tns_transcript *const *transcripts, uint64_t *rounds_out, uint64_t *finals_out,
-                         uint64_t *challenges_out, bool resident, const ScBatchLimits &lim, ScBatchReport *rep);
-// mle_eval.hip: tns_mle_evaluate_batch(_device) with the launch limits as an argument (the entry
-// points pass the defaults, the probe of tests/device/mleevalprobe.hip forces them); rep
-// (optional): the regime, the launches, the blocks and the rows a thread took
-int mle_evaluate_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
-                       const uint64_t *points, uint64_t *values_out, bool resident, const MleEvalLimits &lim,
-                       MleEvalReport *rep);
-// sumcheck_verify.hip: tns_sumcheck_verify_batch(_device) likewise; rep: the one evaluation pass
-int sumcheck_verify_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
-                          const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
-                          tns_transcript *const *transcripts, const uint64_t *rounds, const uint64_t *finals,
-                          uint64_t *challenges_out, uint32_t *n_challenges_out, int *verdicts_out, uint64_t *values_out,
-                          bool resident, const MleEvalLimits &lim, MleEvalReport *rep);
 // abi_host.cpp: a tns_vk's three points, each checked against its curve
 struct Vk {
   G1Affine g1;

@@ -1,6 +1,6 @@
 // api.hip -- the device-side C ABI of include/tns.h: device info, contexts, setup, SRS and SRS files, the KZG /
-// MSM / interpolation / MLE / sum-check entry points, device buffers, the clock probe and the
-// profiler read-out.  (The provers are in prove.hip, the host-only entry points in abi_host.cpp.)
+// MSM / interpolation / MLE entry points, device buffers, the clock probe and the profiler
+// read-out.  (The provers are in prove.hip, the host-only entry points in abi_host.cpp.)
 #include "abi.hpp"
 
 namespace tns {
@@ -570,80 +570,6 @@ int tns_mle_partial_evaluate(tns_ctx *ctx, const uint64_t *evals, size_t n_evals
     TNS_HIP(hipMemcpyAsync(out, src, sizeof(Fr) * (n >> k), hipMemcpyDeviceToHost, ctx->c.stream));
     TNS_HIP(hipStreamSynchronize(ctx->c.stream));
     return TNS_OK;
-  });
-}
-
-static int sumcheck_prove_core(tns_ctx *ctx, Fr *const *ptrs, int n_tables, unsigned nv, const uint64_t claimed[4],
-                               const tns_term *terms, int n_terms, tns_transcript *tr, uint64_t *rounds_out,
-                               uint64_t final_out[4], uint64_t *challenges_out) {
-  std::vector<SumcheckTerm> st(n_terms);
-  for (int t = 0; t < n_terms; t++) {
-    std::memcpy(&st[t].coeff, terms[t].coeff, 32);
-    for (int j = 0; j < 3; j++) st[t].tab[j] = terms[t].tables[j];
-  }
-  Fr cl;
-  std::memcpy(&cl, claimed, 32);
-  std::vector<Fr> rounds(4 * (size_t)(nv ? nv : 1)), chal(nv ? nv : 1);
-  Fr fe;
-  int rc = sumcheck_prove_dev(&ctx->c, ptrs, n_tables, nv, cl, st.data(), n_terms, tr->t, rounds.data(),
-                              chal.data(), &fe);
-  std::memcpy(rounds_out, rounds.data(), 128 * (size_t)nv);
-  if (challenges_out) std::memcpy(challenges_out, chal.data(), 32 * (size_t)nv);
-  std::memcpy(final_out, &fe, 32);
-  return rc;
-}
-
-static void check_sumcheck_shape(unsigned nv, int n_tables, int n_terms) {
-  if (nv > 30 || n_tables < 0 || n_tables > 4 || n_terms < 0)
-    throw Error(TNS_ERR_INVALID_PARAMETERS, "unsupported sum-check shape (<= 4 tables)");
-}
-
-int tns_sumcheck_prove(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv,
-                       const uint64_t claimed[4], const tns_term *terms, int n_terms, tns_transcript *tr,
-                       uint64_t *rounds_out, uint64_t final_out[4], uint64_t *challenges_out) {
-  return guarded([&]() {
-    CtxScope g(&ctx->c);
-    check_sumcheck_shape(nv, n_tables, n_terms);
-    size_t n = (size_t)1 << nv;
-    std::vector<DevBuf> bufs(n_tables);
-    std::vector<Fr *> ptrs(n_tables);
-    for (int i = 0; i < n_tables; i++) {
-      ptrs[i] = (Fr *)bufs[i].ensure(sizeof(Fr) * n);
-      TNS_HIP(hipMemcpyAsync(ptrs[i], tables[i], sizeof(Fr) * n, hipMemcpyHostToDevice, ctx->c.stream));
-    }
-    return sumcheck_prove_core(ctx, ptrs.data(), n_tables, nv, claimed, terms, n_terms, tr, rounds_out, final_out,
-                               challenges_out);
-  });
-}
-
-int tns_composition_sum_device(tns_ctx *ctx, const uint64_t *const *d_tables, int n_tables, unsigned nv,
-                               const tns_term *terms, int n_terms, uint64_t out[4]) {
-  return guarded([&]() {
-    CtxScope g(&ctx->c);
-    check_sumcheck_shape(nv, n_tables, n_terms);
-    std::vector<Fr *> ptrs(n_tables);
-    for (int i = 0; i < n_tables; i++) ptrs[i] = (Fr *)d_tables[i];
-    std::vector<SumcheckTerm> st(n_terms);
-    for (int t = 0; t < n_terms; t++) {
-      std::memcpy(&st[t].coeff, terms[t].coeff, 32);
-      for (int j = 0; j < 3; j++) st[t].tab[j] = terms[t].tables[j];
-    }
-    const Fr s = composition_sum_dev(&ctx->c, ptrs.data(), n_tables, nv, st.data(), n_terms);
-    std::memcpy(out, &s, 32);
-    return TNS_OK;
-  });
-}
-
-int tns_sumcheck_prove_device(tns_ctx *ctx, const uint64_t *const *d_tables, int n_tables, unsigned nv,
-                              const uint64_t claimed[4], const tns_term *terms, int n_terms, tns_transcript *tr,
-                              uint64_t *rounds_out, uint64_t final_out[4], uint64_t *challenges_out) {
-  return guarded([&]() {
-    CtxScope g(&ctx->c);
-    check_sumcheck_shape(nv, n_tables, n_terms);
-    std::vector<Fr *> ptrs(n_tables);
-    for (int i = 0; i < n_tables; i++) ptrs[i] = (Fr *)d_tables[i];  // only read
-    return sumcheck_prove_core(ctx, ptrs.data(), n_tables, nv, claimed, terms, n_terms, tr, rounds_out, final_out,
-                               challenges_out);
   });
 }
 

@@ -1,6 +1,7 @@
 // ctx.hpp -- the per-device context: its streams, its named device workspaces and caches, the lock
-// every entry point takes, the host-input uploader, and the entry points of the modules that work
-// on the context alone (mle.hip, sumcheck.hip, zero_folds.hip, poly.hip, interp.hip).
+// every entry point takes, the host-input uploaders, and the entry points of the modules that work
+// on the context alone (mle.hip, zero_folds.hip, poly.hip, interp.hip).  The generic sum-check
+// family's are sumcheck.hpp's.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -223,49 +224,19 @@ struct CtxScope {
   explicit CtxScope(Ctx *ctx) : c(ctx), lk(ctx->mu) { TNS_HIP(hipSetDevice(ctx->device)); }
 };
 
+// `bytes` of a call's input on the device: resident input as it is, host input uploaded on
+// c->stream into buf (the caller keeps buf until that stream has drained)
+inline const void *on_device(Ctx *c, const void *in, size_t bytes, bool resident, DevBuf &buf) {
+  if (resident) return in;
+  void *p = buf.ensure(bytes ? bytes : 1);
+  if (bytes) TNS_HIP(hipMemcpyAsync(p, in, bytes, hipMemcpyHostToDevice, c->stream));
+  return p;
+}
+
 // ---- module entry points (device-resident pointers; all on ctx->stream) ----
 // mle.hip
 void mle_fold_dev(Ctx *c, const Fr *in, Fr *out, size_t half, const Fr &r);
 Fr mle_evaluate_dev(Ctx *c, const Fr *evals, unsigned nv, const Fr *point_host);
-
-// mle_eval.hip
-// values_host[b k + j] = MLE(tables[j] + b 2^nv)(points_host + b nv) for every instance b and table
-// j < k <= 4 in one pass: every entry read once, at most two launches whatever nv and batch, one
-// synchronise.  lim: the launch geometry's limits (the entry points pass the defaults, the probe
-// of tests/device/mleevalprobe.hip forces them); rep (optional): what ran.
-enum : int { MLE_EVAL_NONE = 0, MLE_EVAL_WAVE = 1, MLE_EVAL_BLOCK = 2, MLE_EVAL_BLOCKS = 3 };
-struct MleEvalLimits {
-  // a thread takes more rows only while the launch keeps this many blocks, and at most
-  // 2^max_log_rows.  Measured (profiles/mle_eval_bench.json rows_sweep): a block's
-  // fixed cost -- the eq_lo products, the block sum and, across blocks, the fence before its
-  // counter increment -- outweighs what more blocks a CU hide, so one block a CU (256 CUs) is the
-  // floor; beyond 64 rows a thread the time is flat
-  size_t min_blocks = 256;
-  unsigned max_log_rows = 6;
-};
-struct MleEvalReport {
-  int regime = MLE_EVAL_NONE;     // how an instance's sum is formed: part of a wave, one block, several blocks
-  size_t launches = 0, blocks = 0, rows_per_thread = 0;  // blocks: of the dot-product launch
-};
-void mle_evaluate_batch_dev(Ctx *c, const Fr *const *tables, int k, unsigned nv, size_t batch, const Fr *points_host,
-                            Fr *values_host, const MleEvalLimits &lim = MleEvalLimits(), MleEvalReport *rep = nullptr);
-
-// sumcheck.hip
-struct SumcheckTerm {
-  Fr coeff;
-  int tab[3];
-};
-struct HostTranscript;
-Fr composition_sum_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const SumcheckTerm *terms, int n_terms);
-// Runs every round of SumCheck::prove over k device tables of 2^nv entries (only read: they are
-// folded into workspace) on the host's transcript.  Returns status; fills rounds (nv x 4), the
-// challenges and the final evaluation.
-int sumcheck_prove_dev(Ctx *c, Fr *const *tables, int k, unsigned nv, const Fr &claimed,
-                       const SumcheckTerm *terms, int n_terms, HostTranscript &tr, Fr *rounds,
-                       Fr *challenges, Fr *final_eval);
-// The nv rounds of a closure that is the constant c everywhere (c = 0: the zero closure of Twist /
-// Shout), on the transcript alone; rounds (nv x 4) and chal (nv) are optional.
-void sumcheck_constant_rounds(HostTranscript &tr, unsigned nv, const Fr &c, Fr *rounds, Fr *chal);
 
 // zero_folds.hip
 // The single chain: binds the k tables at the challenges on stream st and writes their values to

@@ -450,14 +450,6 @@ bool batch_checks(const tns_ctx *ctx, const tns_srs *srs, const void *in, size_t
   return false;
 }
 
-// host rows -> the device (one upload); device rows: as they are
-const Fr *rows_on_device(tns_ctx *ctx, const uint64_t *rows, size_t n, size_t batch, bool resident, DevBuf &d) {
-  if (resident) return (const Fr *)rows;
-  Fr *p = (Fr *)d.ensure(sizeof(Fr) * std::max<size_t>(batch * n, 1));
-  if (batch * n) TNS_HIP(hipMemcpyAsync(p, rows, sizeof(Fr) * batch * n, hipMemcpyHostToDevice, ctx->c.stream));
-  return p;
-}
-
 int batch_call(tns_ctx *ctx, const tns_srs *srs, const uint64_t *in, size_t n, size_t batch, const uint64_t *z,
                uint64_t *values_out, uint64_t *out_affine, BatchOp op, bool resident) {
   return guarded([&]() {
@@ -468,7 +460,7 @@ int batch_call(tns_ctx *ctx, const tns_srs *srs, const uint64_t *in, size_t n, s
     const bool opens = op == OP_OPEN || op == OP_OPEN_POINTS;
     std::vector<Fr> vals(opens ? batch : 0);
     try {
-      const Fr *rows = rows_on_device(ctx, in, n, batch, resident, d);
+      const Fr *rows = (const Fr *)on_device(&ctx->c, in, sizeof(Fr) * batch * n, resident, d);  // (one upload)
       if (op == OP_MSM) {
         msm_batch_srs(&ctx->c, srs->s, rows, n, batch, BatchLimits(), out.data(), nullptr);
       } else if (op == OP_COMMIT) {

@@ -225,14 +225,9 @@ void mle_evaluate_batch_dev(Ctx *c, const Fr *const *tables, int k, unsigned nv,
       rep.blocks = g;
       rep.rows_per_thread = 1;
       TNS_PROF(c, "mle_eval_dot", bytes);
-#define TNS_ME_K(K) k_mle_dot_small<K><<<g, ME_BLOCK, 0, st>>>(tt, d_pts, nv, total, d_vals)
-      switch (k) {
-        case 1: TNS_ME_K(1); break;
-        case 2: TNS_ME_K(2); break;
-        case 3: TNS_ME_K(3); break;
-        default: TNS_ME_K(4); break;
-      }
-#undef TNS_ME_K
+      sc_for_tables(k, [&](auto K) {
+        k_mle_dot_small<decltype(K)::value><<<g, ME_BLOCK, 0, st>>>(tt, d_pts, nv, total, d_vals);
+      });
       TNS_LAUNCH_CHECK();
       rep.launches = 1;
     } else {
@@ -258,14 +253,9 @@ void mle_evaluate_batch_dev(Ctx *c, const Fr *const *tables, int k, unsigned nv,
         TNS_LAUNCH_CHECK();
       }
       TNS_PROF(c, "mle_eval_dot", bytes);
-#define TNS_ME_K(K) k_mle_dot<K><<<g, ME_BLOCK, 0, st>>>(tt, eq_hi, d_pts, nv, log_rpt, d_vals, partials, counters)
-      switch (k) {
-        case 1: TNS_ME_K(1); break;
-        case 2: TNS_ME_K(2); break;
-        case 3: TNS_ME_K(3); break;
-        default: TNS_ME_K(4); break;
-      }
-#undef TNS_ME_K
+      sc_for_tables(k, [&](auto K) {
+        k_mle_dot<decltype(K)::value><<<g, ME_BLOCK, 0, st>>>(tt, eq_hi, d_pts, nv, log_rpt, d_vals, partials, counters);
+      });
       TNS_LAUNCH_CHECK();
       rep.launches = 2;
     }
@@ -274,14 +264,6 @@ void mle_evaluate_batch_dev(Ctx *c, const Fr *const *tables, int k, unsigned nv,
   }
   if (rep_out) *rep_out = rep;
 }
-
-// On every exit nothing queued on the context's stream is still running
-namespace {
-struct MeDrain {
-  Ctx *c;
-  ~MeDrain() { (void)hipStreamSynchronize(c->stream); }
-};
-}  // namespace
 
 int mle_evaluate_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
                        const uint64_t *points, uint64_t *values_out, bool resident, const MleEvalLimits &lim,
@@ -293,26 +275,11 @@ int mle_evaluate_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables
     if (nv > 30 || n_tables < 0 || n_tables > MAX_SC_TABLES)
       throw Error(TNS_ERR_INVALID_PARAMETERS, "unsupported evaluation shape (<= 4 tables, <= 30 variables)");
     if (n_tables == 0) return (int)TNS_OK;
-    if (!tables || !values_out || (nv > 0 && !points)) throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    for (int j = 0; j < n_tables; j++)
-      if (!tables[j]) throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    if (batch > (BATCH_MAX_SCALARS >> nv)) throw Error(TNS_ERR_INVALID_PARAMETERS, "batch * 2^nv exceeds 2^32 entries");
-    const size_t n = (size_t)1 << nv;
+    sc_check_arrays(tables && values_out && (nv == 0 || points), tables, n_tables, batch, nv);
     CtxScope scope(&ctx->c);
     Ctx *c = &ctx->c;
-    DevBuf up[MAX_SC_TABLES];  // the host entry's call-scoped copies
-    MeDrain drain{c};          // (declared after them: it runs before they are freed)
-    const Fr *tabs[MAX_SC_TABLES] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < n_tables; j++) {
-      if (resident) {
-        tabs[j] = (const Fr *)tables[j];  // only read
-      } else {
-        Fr *d = (Fr *)up[j].ensure(sizeof(Fr) * batch * n);
-        TNS_HIP(hipMemcpyAsync(d, tables[j], sizeof(Fr) * batch * n, hipMemcpyHostToDevice, c->stream));
-        tabs[j] = d;
-      }
-    }
-    mle_evaluate_batch_dev(c, tabs, n_tables, nv, batch, (const Fr *)points, (Fr *)values_out, lim, &rep);
+    StagedTables staged(c, tables, n_tables, (sizeof(Fr) * batch) << nv, resident);
+    mle_evaluate_batch_dev(c, staged.tab, n_tables, nv, batch, (const Fr *)points, (Fr *)values_out, lim, &rep);
     return (int)TNS_OK;
   });
   if (rep_out) *rep_out = rep;

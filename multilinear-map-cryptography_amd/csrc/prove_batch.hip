@@ -55,13 +55,6 @@ const Fr *padded_rows(Ctx *c, const uint64_t *in, size_t n_in, size_t N, size_t 
                              resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
   return p;
 }
-// `bytes` of input: resident as they are, else uploaded
-const void *on_device(Ctx *c, const void *in, size_t bytes, bool resident, DevBuf &buf) {
-  if (resident) return in;
-  void *p = buf.ensure(bytes ? bytes : 1);
-  if (bytes) TNS_HIP(hipMemcpyAsync(p, in, bytes, hipMemcpyHostToDevice, c->stream));
-  return p;
-}
 
 struct BatchedProof {
   const char *label[2];        // the commitments' transcript labels (src/twist.rs:170-174, src/shout.rs:137-141)

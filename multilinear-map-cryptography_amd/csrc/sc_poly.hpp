@@ -1,15 +1,28 @@
 // sc_poly.hpp -- what the generic sum-check's round kernels share (sumcheck.hip: one instance;
 // sumcheck_batch.hip: a batch of instances): the nested form of a composition and its evaluation
-// at one point, the lazy-domain arithmetic the rounds run in, and the wave / block reductions.
+// at one point, the lazy-domain arithmetic the rounds run in, the wave / block reductions, and
+// the dispatch of a launch on the table count.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
-#include "ctx.hpp"
-#include "sc_tables.hpp"
+#include "sumcheck.hpp"
 
 namespace tns {
+
+// f(std::integral_constant<int, K>()) for k = K in 1..4 tables (any other k: 4), so that a launch
+// names its kernel's table count at compile time: k_x<decltype(K)::value><<<...>>>(...)
+template <class F>
+static void sc_for_tables(int k, F &&f) {
+  switch (k) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 4>()); break;
+  }
+}
 
 // ---------------------------------------------------------------- generic compositions
 // A degree <= 3 composition sum_t c_t prod_{j in t} T_j over K <= 4 tables is rewritten on the

@@ -13,7 +13,8 @@
 //
 // A composition that no table enters (no terms, or constant terms alone) needs no device: its
 // round polynomials are constants and the transcript alone yields the challenges
-// (sumcheck_constant_rounds, which also serves the zero closure of Twist / Shout, prove.hip).
+// (sumcheck_constant_rounds).  The host's turn of a round -- coefficients, check, transcript,
+// challenge, next claim -- is sumcheck_host.cpp's; the C entry points are sumcheck_front.hip's.
 // Binding tables at challenges known in advance is zero_folds.hip's; a batch of instances in one
 // call is sumcheck_batch.hip's; the composition's nested form and its evaluation, which both share,
 // are sc_poly.hpp's.
@@ -21,11 +22,8 @@
 
 #include <cstring>
 
-#include "ctx.hpp"
-#include "host.hpp"
 #include "hostfield.hpp"
 #include "sc_poly.hpp"
-#include "sc_tables.hpp"
 
 namespace tns {
 
@@ -556,27 +554,17 @@ static uint32_t sc_launch(ScRun &R, const ScTables &tt, size_t P) {
   if (P <= split_max) {  // four lanes a pair, 16 pairs a one-wave block (2^12-2^14 measured alike;
                          // at 2^16 the pairs-per-lane kernel is 2x faster)
     const unsigned g = grid_for(P, 16, R.max_grid * 4);
-#define TNS_SC_K(K) \
-  k_sc_round_split<FOLD, K, SKIP1><<<g, 64, 0, st>>>(tt, R.q_dev, P, R.rd, R.partials, R.counter, R.res_dev, seq)
-    switch (R.k) {
-      case 1: TNS_SC_K(1); break;
-      case 2: TNS_SC_K(2); break;
-      case 3: TNS_SC_K(3); break;
-      default: TNS_SC_K(4); break;
-    }
-#undef TNS_SC_K
+    sc_for_tables(R.k, [&](auto K) {
+      k_sc_round_split<FOLD, decltype(K)::value, SKIP1>
+          <<<g, 64, 0, st>>>(tt, R.q_dev, P, R.rd, R.partials, R.counter, R.res_dev, seq);
+    });
   } else {
     const unsigned bs = P >= ((size_t)1 << 16) ? 256u : 64u;
     const unsigned g = grid_for(P, bs, R.max_grid * (256 / bs));
-#define TNS_SC_K(K) \
-  k_sc_round_poly<FOLD, K, SKIP1><<<g, bs, 0, st>>>(tt, R.q_dev, P, R.rd, R.partials, R.counter, R.res_dev, seq)
-    switch (R.k) {
-      case 1: TNS_SC_K(1); break;
-      case 2: TNS_SC_K(2); break;
-      case 3: TNS_SC_K(3); break;
-      default: TNS_SC_K(4); break;
-    }
-#undef TNS_SC_K
+    sc_for_tables(R.k, [&](auto K) {
+      k_sc_round_poly<FOLD, decltype(K)::value, SKIP1>
+          <<<g, bs, 0, st>>>(tt, R.q_dev, P, R.rd, R.partials, R.counter, R.res_dev, seq);
+    });
   }
   TNS_LAUNCH_CHECK();
   return seq;
@@ -731,16 +719,10 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
         tail_seq = c->sc.seq + 1;
         c->sc.seq += nv - r0 + 1;
         const unsigned g = (unsigned)std::min<size_t>(SC_PTAIL_BLOCKS, std::max<size_t>(1, (n >> (r0 + 1)) / 16));
-#define TNS_SC_K(K)                                                                                             \
-  k_sc_tail<K><<<g, 64, 0, c->stream>>>(pp, R.q_dev, r0, nv, n, R.chal_dev, chal_base, R.res_dev, tail_seq, \
-                                       R.partials, R.counter, sync, rh, htab_dev)
-        switch (k) {
-          case 1: TNS_SC_K(1); break;
-          case 2: TNS_SC_K(2); break;
-          case 3: TNS_SC_K(3); break;
-          default: TNS_SC_K(4); break;
-        }
-#undef TNS_SC_K
+        sc_for_tables(k, [&](auto K) {
+          k_sc_tail<decltype(K)::value><<<g, 64, 0, c->stream>>>(pp, R.q_dev, r0, nv, n, R.chal_dev, chal_base, R.res_dev,
+                                                                 tail_seq, R.partials, R.counter, sync, rh, htab_dev);
+        });
         TNS_LAUNCH_CHECK();
       }
       return tail_seq + (rr - r0);
@@ -782,9 +764,9 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
 #endif
   try {
     Fr cur = claimed;
-    char lab[64];
     uint32_t seq = queue(0);  // (nv == 0: the final kernel, reading the tables as they are)
-    if (nv > 0) tr.prehash(tr.state.size() + strlen("sumcheck_round_0") + 4 * 32 + strlen("sumcheck_challenge_0"));
+    SumcheckLabels lab(0);
+    if (nv > 0) sumcheck_prehash(tr, lab);
     ScHostRounds H;  // (rounds rh .. nv - 1)
     for (unsigned rnd = 0; rnd < nv; rnd++) {
       const uint32_t seq_next = rnd + 1 <= rh ? queue(rnd + 1) : 0;  // (rnd + 1 == rh: the hand-over)
@@ -801,32 +783,23 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
 #if TNS_SC_TRACE
       t_seen[rnd] = us();
 #endif
-      if (rnd > 0) e[1] = sub(cur, e[0]);  // (SKIP1 rounds; round 0 forms g(1) and checks the claim)
+      // (SKIP1 rounds take g(1) from the claim; round 0 forms g(1) and checks the claim)
       Fr coeffs[4];
-      interpolate4_host(e, coeffs);  // lagrange_interpolate of 4 points (src/sumcheck.rs:201-206)
-      if (add(horner_host(coeffs, 4, Fr::zero()), horner_host(coeffs, 4, Fr::one())) != cur) {  // :80-84
-        snprintf(lab, sizeof lab, "Round %u consistency check failed", rnd);
-        throw Error(TNS_ERR_SUMCHECK, lab);
-      }
+      if (!sumcheck_round_coeffs(e, cur, rnd > 0, coeffs))
+        throw Error(TNS_ERR_SUMCHECK, "Round " + std::to_string(rnd) + " consistency check failed");
       for (int x = 0; x < 4; x++) rounds[4 * rnd + x] = coeffs[x];
-      snprintf(lab, sizeof lab, "sumcheck_round_%u", rnd);  // src/sumcheck.rs:90-96
-      tr.append_label(lab);
-      for (int x = 0; x < 4; x++) tr.append_fr(coeffs[x]);
-      snprintf(lab, sizeof lab, "sumcheck_challenge_%u", rnd);
-      const Fr ch = tr.challenge(lab);
+      const Fr ch = sumcheck_absorb_round(tr, lab, coeffs);
       if (rnd < rh) publish(rnd, ch);  // (first: the device's next round waits for it)
       else H.fold(ch);
 #if TNS_SC_TRACE
       t_pub[rnd] = us();
 #endif
       if (challenges) challenges[rnd] = ch;
-      cur = horner_host(coeffs, 4, ch);
+      cur = sumcheck_next_claim(coeffs, ch);
       seq = seq_next;
       if (rnd + 1 < nv) {  // the next challenge's hash over the state so far, while the device works
-        char l1[64], l2[64];
-        const int n1 = snprintf(l1, sizeof l1, "sumcheck_round_%u", rnd + 1);
-        const int n2 = snprintf(l2, sizeof l2, "sumcheck_challenge_%u", rnd + 1);
-        tr.prehash(tr.state.size() + (size_t)n1 + 4 * 32 + (size_t)n2);
+        lab = SumcheckLabels(rnd + 1);
+        sumcheck_prehash(tr, lab);
       }
     }
     const ScResult &res = rh < nv ? *(const ScResult *)c->sc.mapped.p : sc_wait(c, seq);
@@ -863,29 +836,6 @@ static void sumcheck_prove_terms(Ctx *c, Fr *const *tables, int k, unsigned nv, 
     __atomic_store_n(&R.chal->flag, SC_CANCEL, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(c->stream);
     throw;
-  }
-}
-
-
-// ---------------------------------------------------------------- compositions that no table enters
-// All nv rounds of a sum-check whose closure is the constant c at every point (src/sumcheck.rs:
-// 60-100): round rnd's polynomial is the constant c 2^(nv-1-rnd) -- [that, 0, 0, 0] as
-// coefficients -- so the transcript alone yields the challenges.  c = 0 is the zero constraint
-// closure of Twist / Shout (prove.hip zero_closure_transcript).  rounds (nv x 4) and chal (nv)
-// are optional.
-void sumcheck_constant_rounds(HostTranscript &tr, unsigned nv, const Fr &c, Fr *rounds, Fr *chal) {
-  std::vector<Fr> g(nv);  // g[rnd] = c 2^(nv-1-rnd)
-  for (unsigned rnd = nv; rnd-- > 0;) g[rnd] = rnd + 1 == nv ? c : add(g[rnd + 1], g[rnd + 1]);
-  char lab[64];
-  for (unsigned rnd = 0; rnd < nv; rnd++) {
-    const Fr coeffs[4] = {g[rnd], Fr::zero(), Fr::zero(), Fr::zero()};
-    if (rounds) std::memcpy(rounds + 4 * rnd, coeffs, sizeof coeffs);
-    snprintf(lab, sizeof lab, "sumcheck_round_%u", rnd);  // src/sumcheck.rs:90-96
-    tr.append_label(lab);
-    for (int x = 0; x < 4; x++) tr.append_fr(coeffs[x]);
-    snprintf(lab, sizeof lab, "sumcheck_challenge_%u", rnd);
-    const Fr ch = tr.challenge(lab);
-    if (chal) chal[rnd] = ch;
   }
 }
 

@@ -219,15 +219,10 @@ void scb_launch_round(hipStream_t st, int k, const ScTables &tt, const ScPoly *q
   const unsigned log_ipt = logP > SCB_BLOCK_LOG ? scb_log_ipt(logP, total) : 0;
   const uint64_t per = (uint64_t)SCB_BLOCK << log_ipt;
   const unsigned g = (unsigned)((total + per - 1) / per);
-#define TNS_SCB_K(K) \
-  k_scb_round<K, FIRST><<<g, SCB_BLOCK, 0, st>>>(tt, q_dev, logP, log_ipt, total, d_chal, d_sums, partials, counters)
-  switch (k) {
-    case 1: TNS_SCB_K(1); break;
-    case 2: TNS_SCB_K(2); break;
-    case 3: TNS_SCB_K(3); break;
-    default: TNS_SCB_K(4); break;
-  }
-#undef TNS_SCB_K
+  sc_for_tables(k, [&](auto K) {
+    k_scb_round<decltype(K)::value, FIRST>
+        <<<g, SCB_BLOCK, 0, st>>>(tt, q_dev, logP, log_ipt, total, d_chal, d_sums, partials, counters);
+  });
   TNS_LAUNCH_CHECK();
 }
 
@@ -277,20 +272,11 @@ size_t scb_group(const ScbCall &A, const ScPoly *q_dev, const int *perm, size_t 
   auto out_of = [&](unsigned rr, int m) -> Fr * {
     return rr % 2 == 1 ? ping + (size_t)m * G * (n / 2) : pong + (size_t)m * G * (n / 4);
   };
-  auto prehash_all = [&](unsigned rnd) {  // the next challenge's hash over the state so far, while the device works
-    char l1[64], l2[64];
-    const int n1 = snprintf(l1, sizeof l1, "sumcheck_round_%u", rnd);
-    const int n2 = snprintf(l2, sizeof l2, "sumcheck_challenge_%u", rnd);
-    for (size_t b = 0; b < G; b++) {
-      HostTranscript &tr = A.trs[g0 + b]->t;
-      tr.prehash(tr.state.size() + (size_t)n1 + 4 * 32 + (size_t)n2);
-    }
-  };
   std::vector<Fr> cur(A.claimed + g0, A.claimed + g0 + G);
   size_t launches = 0;
-  char lab_r[64], lab_c[64];
   for (unsigned rnd = 0; rnd < nv; rnd++) {
     const unsigned logP = nv - 1 - rnd;
+    const SumcheckLabels lab(rnd);
     ScTables tt{};
     for (int m = 0; m < k; m++) {
       tt.in[m] = in_of(rnd, m);
@@ -301,27 +287,20 @@ size_t scb_group(const ScbCall &A, const ScPoly *q_dev, const int *perm, size_t 
     else scb_launch_round<false>(st, k, tt, q_dev, logP, total, d_chal, d_sums, partials, counters);
     launches++;
     TNS_HIP(hipMemcpyAsync(h_sums, d_sums, sizeof(Fr) * 4 * G, hipMemcpyDeviceToHost, st));
-    prehash_all(rnd);
+    // the round's challenge hash over each state so far, while the device works
+    for (size_t b = 0; b < G; b++) sumcheck_prehash(A.trs[g0 + b]->t, lab);
     TNS_HIP(hipStreamSynchronize(st));
-    snprintf(lab_r, sizeof lab_r, "sumcheck_round_%u", rnd);  // src/sumcheck.rs:90-96
-    snprintf(lab_c, sizeof lab_c, "sumcheck_challenge_%u", rnd);
-    for (size_t b = 0; b < G; b++) {  // the single prover's turn (sumcheck_prove_terms), per instance
-      Fr e[4] = {h_sums[4 * b], h_sums[4 * b + 1], h_sums[4 * b + 2], h_sums[4 * b + 3]};
-      if (rnd > 0) e[1] = sub(cur[b], e[0]);  // (round 0 forms g(1) and checks the claim)
-      Fr coeffs[4];
-      interpolate4_host(e, coeffs);  // lagrange_interpolate of 4 points (src/sumcheck.rs:201-206)
-      // :80-84.  Only round 0 can fail it (later rounds take g(1) from the claim), and the instances
+    for (size_t b = 0; b < G; b++) {  // the host's turn (sumcheck_host.cpp), per instance
+      // Only round 0 can fail the check (later rounds take g(1) from the claim), and the instances
       // are visited in order: the first failure seen is the lowest instance of the earliest round
-      if (add(horner_host(coeffs, 4, Fr::zero()), horner_host(coeffs, 4, Fr::one())) != cur[b]) scb_fail_round(g0 + b, rnd);
-      HostTranscript &tr = A.trs[g0 + b]->t;
+      Fr coeffs[4];
+      if (!sumcheck_round_coeffs(h_sums + 4 * b, cur[b], rnd > 0, coeffs)) scb_fail_round(g0 + b, rnd);
       Fr *rounds = A.rounds + ((g0 + b) * nv + rnd) * 4;
       for (int x = 0; x < 4; x++) rounds[x] = coeffs[x];
-      tr.append_label(lab_r);
-      for (int x = 0; x < 4; x++) tr.append_fr(coeffs[x]);
-      const Fr ch = tr.challenge(lab_c);
+      const Fr ch = sumcheck_absorb_round(A.trs[g0 + b]->t, lab, coeffs);
       h_chal[b] = ch;
       A.chal[(g0 + b) * nv + rnd] = ch;
-      cur[b] = horner_host(coeffs, 4, ch);
+      cur[b] = sumcheck_next_claim(coeffs, ch);
     }
     // (h_chal is rewritten only after the next round's synchronise: the copy has landed by then)
     TNS_HIP(hipMemcpyAsync(d_chal, h_chal, sizeof(Fr) * G, hipMemcpyHostToDevice, st));
@@ -351,12 +330,6 @@ size_t scb_group(const ScbCall &A, const ScPoly *q_dev, const int *perm, size_t 
   return launches;
 }
 
-// On every exit nothing queued on the context's stream is still running
-struct ScbDrain {
-  Ctx *c;
-  ~ScbDrain() { (void)hipStreamSynchronize(c->stream); }
-};
-
 }  // namespace
 
 int sumcheck_prove_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
@@ -368,31 +341,13 @@ int sumcheck_prove_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tabl
     // ---- the checks, before anything touches a device
     if (!ctx) throw Error(TNS_ERR_INVALID_PARAMETERS, "null context");
     if (batch == 0) return (int)TNS_OK;
-    if (nv > 30 || n_tables < 0 || n_tables > MAX_SC_TABLES || n_terms < 0)
-      throw Error(TNS_ERR_INVALID_PARAMETERS, "unsupported sum-check shape (<= 4 tables)");
-    if (!claimed_sums || !transcripts || !finals_out || (nv > 0 && !rounds_out) || (n_terms > 0 && !terms) ||
-        (n_tables > 0 && !tables))
-      throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    for (int j = 0; j < n_tables; j++)
-      if (!tables[j]) throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    if (batch > (BATCH_MAX_SCALARS >> nv)) throw Error(TNS_ERR_INVALID_PARAMETERS, "batch * 2^nv exceeds 2^32 entries");
-    {
-      std::vector<const tns_transcript *> seen(transcripts, transcripts + batch);
-      for (const tns_transcript *t : seen)
-        if (!t) throw Error(TNS_ERR_INVALID_PARAMETERS, "null transcript handle");
-      std::sort(seen.begin(), seen.end());
-      if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-        throw Error(TNS_ERR_INVALID_PARAMETERS, "the same transcript handle twice in one batch");
-    }
-    std::vector<SumcheckTerm> st(n_terms);
+    sc_check_shape(nv, n_tables, n_terms);
+    sc_check_arrays(claimed_sums && transcripts && finals_out && (nv == 0 || rounds_out) && (n_terms == 0 || terms) &&
+                        (n_tables == 0 || tables),
+                    tables, n_tables, batch, nv);
+    sc_check_transcripts(transcripts, batch);
     ScBatchShape shape;
-    for (int t = 0; t < n_terms; t++) {
-      std::memcpy(&st[t].coeff, terms[t].coeff, 32);
-      for (int j = 0; j < 3; j++) {
-        st[t].tab[j] = terms[t].tables[j];
-        shape.table_terms = shape.table_terms || st[t].tab[j] >= 0;
-      }
-    }
+    const std::vector<SumcheckTerm> st = sc_terms(terms, n_terms, &shape.table_terms);
     sc_check_terms(st.data(), n_terms, n_tables);
     shape.batch = batch;
     shape.nv = nv;
@@ -405,17 +360,8 @@ int sumcheck_prove_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tabl
     const size_t n = (size_t)1 << nv;
     CtxScope scope(&ctx->c);
     Ctx *c = &ctx->c;
-    DevBuf up[MAX_SC_TABLES];  // the host entry's call-scoped copies
-    ScbDrain drain{c};         // (declared after them: it runs before they are freed)
-    Fr *tabs[MAX_SC_TABLES] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < n_tables; j++) {
-      if (resident) {
-        tabs[j] = (Fr *)tables[j];  // only read
-      } else {
-        tabs[j] = (Fr *)up[j].ensure(sizeof(Fr) * batch * n);
-        TNS_HIP(hipMemcpyAsync(tabs[j], tables[j], sizeof(Fr) * batch * n, hipMemcpyHostToDevice, c->stream));
-      }
-    }
+    StagedTables staged(c, tables, n_tables, sizeof(Fr) * batch * n, resident);
+    Fr *const *tabs = staged.tab;
     std::vector<Fr> rounds(4 * (size_t)nv * batch + 1), chal((size_t)nv * batch + 1), fin(batch), cl(batch);
     std::memcpy((void *)cl.data(), claimed_sums, sizeof(Fr) * batch);
 

@@ -5,7 +5,7 @@
 // current_sum == proof.final_evaluation: two numbers the prover supplied.  A proof is checked once
 // final_evaluation is compared with the composition at the challenge point, one
 // MultilinearExtension::evaluate (src/polynomials.rs:85-122) a table an instance.  Here:
-//   1. the host replays every instance on its own transcript (sumcheck_replay_host, verify.cpp);
+//   1. the host replays every instance on its own transcript (sumcheck_replay_host, sumcheck_host.cpp);
 //   2. ONE mle_evaluate_batch_dev pass (mle_eval.hip) evaluates every table of every instance at
 //      the instance's challenges -- at most two launches whatever nv and batch; instances whose
 //      replay failed ride along at the zero point;
@@ -15,13 +15,6 @@
 #include "sc_poly.hpp"
 
 namespace tns {
-
-namespace {
-struct SvDrain {  // on every exit nothing queued on the context's stream is still running
-  Ctx *c;
-  ~SvDrain() { (void)hipStreamSynchronize(c->stream); }
-};
-}  // namespace
 
 int sumcheck_verify_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tables, unsigned nv, size_t batch,
                           const uint64_t *claimed_sums, const tns_term *terms, int n_terms,
@@ -33,27 +26,11 @@ int sumcheck_verify_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tab
     // ---- the checks, before anything touches a transcript or a device
     if (!ctx) throw Error(TNS_ERR_INVALID_PARAMETERS, "null context");
     if (batch == 0) return (int)TNS_OK;
-    if (nv > 30 || n_tables < 0 || n_tables > MAX_SC_TABLES || n_terms < 0)
-      throw Error(TNS_ERR_INVALID_PARAMETERS, "unsupported sum-check shape (<= 4 tables)");
-    if (!claimed_sums || !transcripts || !finals || !verdicts_out || (nv > 0 && !rounds) || (n_terms > 0 && !terms))
-      throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    if (tables)
-      for (int j = 0; j < n_tables; j++)
-        if (!tables[j]) throw Error(TNS_ERR_INVALID_PARAMETERS, "null input or output array");
-    if (batch > (BATCH_MAX_SCALARS >> nv)) throw Error(TNS_ERR_INVALID_PARAMETERS, "batch * 2^nv exceeds 2^32 entries");
-    {
-      std::vector<const tns_transcript *> seen(transcripts, transcripts + batch);
-      for (const tns_transcript *t : seen)
-        if (!t) throw Error(TNS_ERR_INVALID_PARAMETERS, "null transcript handle");
-      std::sort(seen.begin(), seen.end());
-      if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-        throw Error(TNS_ERR_INVALID_PARAMETERS, "the same transcript handle twice in one batch");
-    }
-    std::vector<SumcheckTerm> st(n_terms);
-    for (int t = 0; t < n_terms; t++) {
-      std::memcpy(&st[t].coeff, terms[t].coeff, 32);
-      for (int j = 0; j < 3; j++) st[t].tab[j] = terms[t].tables[j];
-    }
+    sc_check_shape(nv, n_tables, n_terms);
+    sc_check_arrays(claimed_sums && transcripts && finals && verdicts_out && (nv == 0 || rounds) && (n_terms == 0 || terms),
+                    tables, n_tables, batch, nv);
+    sc_check_transcripts(transcripts, batch);
+    const std::vector<SumcheckTerm> st = sc_terms(terms, n_terms);
     sc_check_terms(st.data(), n_terms, n_tables);
 
     // ---- 1. the replay, per instance (src/sumcheck.rs:124-152)
@@ -80,19 +57,8 @@ int sumcheck_verify_batch(tns_ctx *ctx, const uint64_t *const *tables, int n_tab
           if (verdict[b] == 0) std::copy(chal.begin() + (size_t)nv * b, chal.begin() + (size_t)nv * (b + 1), pts.begin() + (size_t)nv * b);
         CtxScope scope(&ctx->c);
         Ctx *c = &ctx->c;
-        DevBuf up[MAX_SC_TABLES];  // the host entry's call-scoped copies
-        SvDrain drain{c};          // (declared after them: it runs before they are freed)
-        const Fr *tabs[MAX_SC_TABLES] = {nullptr, nullptr, nullptr, nullptr};
-        for (int j = 0; j < n_tables; j++) {
-          if (resident) {
-            tabs[j] = (const Fr *)tables[j];  // only read
-          } else {
-            Fr *d = (Fr *)up[j].ensure(sizeof(Fr) * batch * n);
-            TNS_HIP(hipMemcpyAsync(d, tables[j], sizeof(Fr) * batch * n, hipMemcpyHostToDevice, c->stream));
-            tabs[j] = d;
-          }
-        }
-        mle_evaluate_batch_dev(c, tabs, n_tables, nv, batch, pts.data(), vals.data(), lim, &rep);
+        StagedTables staged(c, tables, n_tables, sizeof(Fr) * batch * n, resident);
+        mle_evaluate_batch_dev(c, staged.tab, n_tables, nv, batch, pts.data(), vals.data(), lim, &rep);
       }
       for (size_t b = 0; b < batch; b++) {
         Fr *v = vals.data() + (size_t)n_tables * b;

@@ -1,6 +1,6 @@
 // verify.cpp -- the verifiers of the reference, on the host:
 //   KZGCommitment::verify / batch_verify   src/commitments.rs:201-301
-//   SumCheck::verify                       src/sumcheck.rs:113-150
+//   (SumCheck::verify is sumcheck_host.cpp's)
 //   Twist::verify, Shout::verify           src/twist.rs:255-304, src/shout.rs:225-274
 //   CommitmentVerificationKey              src/utils.rs:64-75, :104-112 (g2_tau = tau * G2)
 // Restated step by step, including batch_verify's pairing equation exactly as written
@@ -139,34 +139,6 @@ void verify_challenges_host(const uint8_t seed[32], uint64_t first, size_t count
     o[2] = o[3] = 0;
     if (!(o[0] | o[1])) o[0] = 1;
   }
-}
-
-// SumCheck::verify's loop (src/sumcheck.rs:124-152); round polynomials are 4 coefficients
-// (evaluate_round_polynomial = Horner, :209-212)
-int sumcheck_replay_host(HostTranscript &tr, const Fr &claimed, const Fr *rounds, unsigned nv, const Fr &final_eval,
-                         Fr *chal, unsigned *n_chal) {
-  Fr cur = claimed;
-  char lab[64];
-  if (n_chal) *n_chal = 0;
-  for (unsigned r = 0; r < nv; r++) {
-    const Fr *c = rounds + 4 * (size_t)r;
-    const Fr g0 = horner_host(c, 4, Fr::zero()), g1 = horner_host(c, 4, Fr::one());
-    if (add(g0, g1) != cur) return 1;  // :132-134, before the round is appended
-    snprintf(lab, sizeof lab, "sumcheck_round_%u", r);
-    tr.append_label(lab);
-    for (int x = 0; x < 4; x++) tr.append_fr(c[x]);
-    snprintf(lab, sizeof lab, "sumcheck_challenge_%u", r);
-    const Fr ch = tr.challenge(lab);
-    if (chal) chal[r] = ch;
-    if (n_chal) *n_chal = r + 1;
-    cur = horner_host(c, 4, ch);
-  }
-  return cur == final_eval ? 0 : 2;
-}
-
-// SumCheck::verify with claimed sum 0 (src/sumcheck.rs:113-150)
-bool sumcheck_verify_host(HostTranscript &tr, const Fr *rounds, unsigned nv, const Fr &final_eval) {
-  return sumcheck_replay_host(tr, Fr::zero(), rounds, nv, final_eval, nullptr, nullptr) == 0;
 }
 
 // Twist::verify / Shout::verify: labels of the two commitments differ

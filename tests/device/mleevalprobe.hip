@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "abi.hpp"
+#include "sumcheck.hpp"
 
 namespace {
 using namespace tns;

@@ -93,6 +93,28 @@ def test_generic_sumcheck_wrong_claim_at_scale():
     ts.SumCheck(nv, claim).prove_resident(d, terms, ts.Transcript(bytes(32)))
 
 
+def test_generic_sumcheck_wrong_claim_from_host_tables():
+    """The single host entry's error path: its call-scoped device copies of the tables are freed
+    behind a failed proof (the stream drained first), and the same context then proves the true
+    claim through both entries, equal to the fold oracle."""
+    nv = 6
+    terms = COMPOSITIONS["twist_like"]
+    tabs = rand_tables(3, nv, seed=11)
+    T = host_threads()
+    claim = co.fast_composition_sum(tabs, nv, terms, T)
+    st, rounds, fin, chal = co.fast_sumcheck_prove(tabs, nv, claim, terms, threads=T)
+    assert st == 0
+    with pytest.raises(ts.SumCheckError):
+        ts.SumCheck(nv, claim + 1).prove(tabs, terms, ts.Transcript(bytes(32)))
+    proof, chals = ts.SumCheck(nv, claim).prove(tabs, terms, ts.Transcript(bytes(32)), return_challenges=True)
+    assert proof.round_polynomials == [co.fr_ints(r) for r in rounds]
+    assert proof.final_evaluation == co.fr_ints(fin)[0]
+    assert chals == co.fr_ints(chal)
+    d = [ts.DeviceBuffer(ts.Context.get(0), t) for t in tabs]
+    p2, c2 = ts.SumCheck(nv, claim).prove_resident(d, terms, ts.Transcript(bytes(32)))
+    assert p2 == proof and c2 == chals
+
+
 @pytest.mark.parametrize("name", ["twist_like", "dense4"])
 @pytest.mark.parametrize("nv", [0, 1, 2, 3, 4, 5, 13, 14, 15, 16])
 def test_generic_sumcheck_schedule_regimes(name, nv):
