@@ -41,7 +41,7 @@
 
 namespace tns {
 
-constexpr int RED_L = 16;  // running-sum group size of the bucket reduction
+// (RED_L, FIX_FAN, FIX_LEVELS, FIX_WAVE_SPAN and the tail's geometry: msm_plan.hpp)
 
 // *bits = max over i of bitlen(canonical scalar_i); canon (optional) = the canonical scalars
 // (the bucket sort canonicalises Montgomery scalars itself, so the MSMs pass none)
@@ -74,8 +74,6 @@ __device__ __forceinline__ uint32_t bucket_of(const uint32_t *__restrict__ bstar
   }
   return (uint32_t)lo;
 }
-
-constexpr int FIX_FAN = 8;  // short peel chains: single-thread add chains are latency-bound
 
 // keys == nullptr (values-only sort tail): a chunk finds its first bucket by a binary search of the
 // bucket starts and every later run boundary from the next start -- no key per entry.
@@ -173,8 +171,7 @@ __global__ void __launch_bounds__(256) k_accumulate(const uint32_t *__restrict__
 // chunk heads are summed through a FIX_FAN-ary hierarchy so no thread walks a long run.
 // Level l >= 1, group g covers chunks [g F^l, (g+1) F^l) (F = FIX_FAN); its sum is formed only when
 // every sorted entry of those chunks has one key (then every head in it is a full-chunk
-// sum of that bucket); other groups are never read.
-constexpr int FIX_LEVELS = 8;
+// sum of that bucket); other groups are never read.  (n and len: fix_level_sizes, msm_plan.hpp)
 struct FixLevels {
   G1Xyzz *lv[FIX_LEVELS + 1];  // lv[l] for l >= 1 (the level-0 heads live in ht)
   size_t len[FIX_LEVELS + 1];
@@ -241,8 +238,7 @@ __global__ void __launch_bounds__(256) k_fix_level(FixLevelArgs A, int level) {
 // MSM (a skewed input puts every entry in one bucket: Shout's identity lookups, 5.8 instead of
 // 6.4 ms at 2^20).  Shorter runs stay one thread each -- thousands of moderately heavy buckets
 // (the top window's narrow digits crowd the low ones) are cheaper so than as thousands of
-// mostly idle wave passes next to the other lane's accumulation.
-constexpr size_t FIX_WAVE_SPAN = 512;
+// mostly idle wave passes next to the other lane's accumulation.  (FIX_WAVE_SPAN: msm_plan.hpp)
 
 // the items of a run across chunks tf < tl, in order: tail(tf), head(tl), then the inner heads
 // (tf, tl), peeled to FIX_FAN-aligned ranges and climbing a level whenever both ends are aligned
@@ -579,7 +575,7 @@ const FixedBase *srs_fixed_base(Ctx *c, const Srs &srs, size_t n) {
 // sum over each set of the sets x n array X (device) -> out (sets, device)
 static void sum_sets(hipStream_t st, G1Xyzz *X, int sets, size_t n, G1Xyzz *tmp, G1Xyzz *out) {
   G1Xyzz *src = X, *dst = tmp;
-  while (n > 128 && n % 8 == 0) {  // short chains: these passes are latency-bound
+  while (sum_sets_splits(n)) {  // short chains: these passes are latency-bound
     const size_t n_out = (size_t)sets * (n / 8);
     k_sum_chunks<<<grid_for(n_out, 64, 1u << 30), 64, 0, st>>>(src, n_out, 8, dst);
     TNS_LAUNCH_CHECK();
@@ -602,6 +598,8 @@ struct MsmJob {
   void expect(MsmStage s, const char *what) const { if (stage != s) throw Error(TNS_ERR_DEVICE, what); }
   MsmPlan P;
   int L0 = 0, nbits = 0, specs = 0;
+  TailGeom tail;       // what msm_launch_tails ran with, and the fix levels it built
+  int fix_levels = 0;
   BucketSortJob bs;
   hipEvent_t sorted_ev = nullptr;   // recorded on the lane once the bucket order exists
   std::unique_ptr<ProfScope> sort_prof;  // "msm_sort" timing from pass 1 to the last pass
@@ -919,18 +917,15 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     for (int j = 0; j < nj; j++) {
       MsmJob &X = *J[j];
       FixLevels &F = FA.s[j].F;
-      size_t groups = X.nchunks / FIX_FAN, off = 0;
-      while (F.n < FIX_LEVELS && groups >= 2) {  // level sizes: nchunks/F, /F^2, ...
-        F.len[F.n + 1] = groups;
-        off += groups;
-        groups /= FIX_FAN;
-        F.n++;
-      }
+      const FixLevelSizes sz = fix_level_sizes(X.nchunks);  // nchunks/F, /F^2, ...
+      F.n = sz.n;
+      for (int l = 1; l <= sz.n; l++) F.len[l] = sz.len[l];
       if (F.n) {
-        G1Xyzz *base = (G1Xyzz *)X.lane->msm.fix.ensure(sizeof(G1Xyzz) * off);
+        G1Xyzz *base = (G1Xyzz *)X.lane->msm.fix.ensure(sizeof(G1Xyzz) * sz.total);
         size_t o = 0;
         for (int l = 1; l <= F.n; o += F.len[l], l++) F.lv[l] = base + o;
       }
+      X.fix_levels = F.n;
       max_levels = std::max(max_levels, F.n);
       FA.s[j] = FixupSet{X.bstart, X.bend, X.valid, X.ht, F, X.buckets, X.P.nb, X.acc_k};
       max_nb = std::max(max_nb, X.P.nb);
@@ -951,23 +946,11 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     k_bucket_fixup<<<dim3(grid_for(max_nb, 256), nj), 256, 0, st>>>(FA);
     TNS_LAUNCH_CHECK();
   }
-  // bucket reduction (see the header): running sums over groups of L0 buckets, then
-  // the weighted group sum  sum_g g S_g = sum_b 2^b M_b,  M_b = sum_{g: bit b of g} S_g,
-  // as nbits + 2 plain sums (the M_b and sum_g T_g in two halves) -- short dependency chains only.
-  // Up to 2^19 buckets per set the chains are the latency: groups of 4 and masked-sum chunks of 8
-  // (C2, 2^20 points: 2.73 -> 2.65 ms); from 2^21 buckets groups of 16 stay the fastest (2^22,
-  // 2^24; 8: +0.19 ms, 32: +0.63 ms per C4 step, r05 A/B).  c >= 4: half >= 8, so g >= 2.
+  // bucket reduction (see the header; its group sizes, chunks and sums: tail_geom, msm_plan.hpp)
   const int sets = P.Wr * nj;
-  const bool small_sets = P.half <= ((size_t)1 << 19);
-  int L0 = (int)std::min<size_t>(small_sets ? 4 : RED_L, P.half / 2);
-  const size_t g1 = P.half / L0;
-  // a second level (k_reduce_level2, groups of L1 = 4) when the first leaves many groups
-  int L1 = g1 >= ((size_t)1 << 13) ? 4 : 0;
-  if (L1 && g1 / L1 < 2) L1 = 0;
-  const size_t g = L1 ? g1 / L1 : g1;
-  int nbits = 0;
-  while (((size_t)1 << nbits) < g) nbits++;
-  const int specs = nbits + 2;
+  const TailGeom G = tail_geom(P.half);
+  const int L0 = G.L0, L1 = G.L1, nbits = G.nbits, specs = G.specs;
+  const size_t g1 = G.g1, g = G.g;
   {
     TNS_PROF_ON(ctx, st, "msm_reduce", 128.0 * P.nb * nj);
     G1Xyzz *T = (G1Xyzz *)run.msm.level_sums.ensure(sizeof(G1Xyzz) * 2 * sets * (g1 + (L1 ? g : 0)));
@@ -976,23 +959,18 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     TNS_LAUNCH_CHECK();
     if (L1) {
       G1Xyzz *V = S + (size_t)sets * g1, *S2 = V + (size_t)sets * g;
-      int lg0 = 0;
-      while ((1 << lg0) < L0) lg0++;
-      k_reduce_level2<<<grid_for((size_t)sets * g, 64, 1u << 30), 64, 0, st>>>(T, S, sets, g1, L1, lg0, V, S2);
+      k_reduce_level2<<<grid_for((size_t)sets * g, 64, 1u << 30), 64, 0, st>>>(T, S, sets, g1, L1, G.lg0, V, S2);
       TNS_LAUNCH_CHECK();
       T = V;
       S = S2;
-      L0 *= L1;  // the masked sums' weight (msm_complete's doublings)
     }
-    const int CH = (int)std::min<size_t>(small_sets || L1 ? 8 : 16, g / 2);
-    const size_t nch = g / (2 * (size_t)CH);
-    const size_t nparts = (size_t)sets * specs * nch;
+    const size_t nparts = (size_t)sets * specs * G.nch;
     G1Xyzz *parts = (G1Xyzz *)run.msm.parts.ensure(sizeof(G1Xyzz) * (2 * nparts + (size_t)sets * specs));
     G1Xyzz *tmp = parts + nparts, *out = tmp + nparts;
-    const bool tree = nch % 64 == 0;  // each wave adds its 64 chunk sums by a butterfly
-    k_masked_sums<<<grid_for(nparts, 64, 1u << 30), 64, 0, st>>>(T, S, sets, g, nbits, CH, parts, tree);
+    // (G.tree: each wave adds its 64 chunk sums by a butterfly)
+    k_masked_sums<<<grid_for(nparts, 64, 1u << 30), 64, 0, st>>>(T, S, sets, g, nbits, G.CH, parts, G.tree);
     TNS_LAUNCH_CHECK();
-    sum_sets(st, parts, sets * specs, tree ? nch / 64 : nch, tmp, out);
+    sum_sets(st, parts, sets * specs, G.sum_n, tmp, out);
     // the per-set sums, then each MSM's number of sorted non-zero digits (= mixed additions of
     // k_accumulate, profiling)
     const void *src[3] = {out, J[0]->valid, nj == 2 ? J[1]->valid : nullptr};
@@ -1001,20 +979,19 @@ static void msm_launch_tails(Ctx *ctx, MsmJob *const *J, int nj, MsmLane &run) {
     else lane_publish(run, LANE_SLOT_SUMS, 1 + nj, src, by);
   }
   for (int j = 0; j < nj; j++) {
-    J[j]->L0 = L0;
+    J[j]->L0 = G.weight;  // the masked sums' weight (msm_window_sums' doublings)
     J[j]->nbits = nbits;
     J[j]->specs = specs;
+    J[j]->tail = G;
   }
 }
 
-// Wait for the tail's readback and finish on the host: R = sum_g T_g + L0 * sum_b 2^b M_b per
-// set, then Horner over the windows (per-window layout).
-static G1Xyzz msm_complete(Ctx *ctx, MsmJob &J) {
-  if (J.stage == MsmStage::Immediate) return G1Xyzz::inf();
-  const void *hp = lane_wait(J.res_lane ? *J.res_lane : *J.lane, LANE_SLOT_SUMS);
-  if (J.stage == MsmStage::Tiny) return *(const G1Xyzz *)hp;
+// The host finish of a sorted MSM, first half: wait for the tail's readback, then per bucket set
+// R = sum_g T_g + L0 * sum_b 2^b M_b -- the window sums (per-window layout) or the result (shared).
+static std::vector<G1Xyzz> msm_window_sums(Ctx *ctx, MsmJob &J) {
+  J.expect(MsmStage::Sorted, "window sums of an MSM without a bucket order");
   const MsmPlan &P = J.P;
-  const G1Xyzz *all = (const G1Xyzz *)hp;
+  const G1Xyzz *all = (const G1Xyzz *)lane_wait(J.res_lane ? *J.res_lane : *J.lane, LANE_SLOT_SUMS);
   const G1Xyzz *fin = all + (size_t)J.res_set * P.Wr * J.specs;
   const uint32_t *cnt = (const uint32_t *)(all + (size_t)J.res_sets * P.Wr * J.specs);
   ctx->prof.add_ops("msm_accumulate", (double)cnt[J.res_set]);
@@ -1026,6 +1003,11 @@ static G1Xyzz msm_complete(Ctx *ctx, MsmJob &J) {
     for (int L = J.L0; L > 1; L >>= 1) acc = xyzz_dbl(acc);
     Rw[r] = xyzz_add(xyzz_add(f[J.nbits], f[J.nbits + 1]), acc);
   }
+  return Rw;
+}
+
+// ... second half: Horner over the windows (per-window layout) or nothing (shared layout)
+static G1Xyzz msm_horner(const MsmPlan &P, const std::vector<G1Xyzz> &Rw) {
   if (P.shared) return Rw[0];
   G1Xyzz acc = Rw[P.W - 1];
   for (int w = P.W - 2; w >= 0; w--) {
@@ -1033,6 +1015,13 @@ static G1Xyzz msm_complete(Ctx *ctx, MsmJob &J) {
     acc = xyzz_add(acc, Rw[w]);
   }
   return acc;
+}
+
+// Wait for the tail's readback and finish on the host
+static G1Xyzz msm_complete(Ctx *ctx, MsmJob &J) {
+  if (J.stage == MsmStage::Immediate) return G1Xyzz::inf();
+  if (J.stage == MsmStage::Tiny) return *(const G1Xyzz *)lane_wait(J.res_lane ? *J.res_lane : *J.lane, LANE_SLOT_SUMS);
+  return msm_horner(J.P, msm_window_sums(ctx, J));
 }
 
 // a whole MSM queued on a lane (one host wait for the bit length, one inside the sort) for msm_complete
@@ -1050,6 +1039,56 @@ G1Xyzz msm_dev(Ctx *ctx, const G1Affine *points, const Fr *scalars, size_t n, co
   MsmJob J;
   msm_queue_whole(ctx, ctx->lanes[0], MsmArgs{points, scalars, n, fb, fb_off}, J);
   return msm_complete(ctx, J);
+}
+
+// The stages after the sort alone (msm.hpp): jobs filled at stage Sorted, then the same
+// msm_launch_accumulate, msm_launch_tails and host finish as msm_dev / msm_pair_dev -- no launch
+// sequence of its own.  Set j takes lane j's workspaces, as a pair's MSMs do, and everything is
+// queued on lane 0's stream; two sets' buckets adjoin in lane 0's buffer, as msm_pair_queue arranges.
+void msm_from_order_dev(Ctx *ctx, const MsmPlan &P, const OrderedSet *sets, int nj, OrderedMsm &out) {
+  if (nj < 1 || nj > 2 || P.nb == 0 || P.nb != (size_t)P.Wr * P.half || (nj == 2 && !P.shared))
+    throw Error(TNS_ERR_INVALID_PARAMETERS, "MSM from a bucket order: one set, or two of the shared layout");
+  MsmLane &run = ctx->lanes[0];
+  MsmJob J[2];
+  try {
+    for (int j = 0; j < nj; j++) {
+      const OrderedSet &s = sets[j];
+      if (!s.order.vals || !s.order.bstart || !s.valid || !s.points || s.acc_k < 1 || s.nchunks < 1)
+        throw Error(TNS_ERR_INVALID_PARAMETERS, "MSM from a bucket order: a set without its order");
+      MsmJob &X = J[j];
+      X.lane = &ctx->lanes[j];
+      X.ctx = ctx;
+      X.P = P;
+      X.points = s.points;
+      X.keys2 = s.order.keys;
+      X.vals2 = s.order.vals;
+      X.bstart = s.order.bstart;
+      X.bend = s.order.bstart + 1;
+      X.ks = s.order.ks;
+      X.valid = s.valid;
+      X.acc_k = s.acc_k;
+      X.nchunks = s.nchunks;
+      X.n = s.order.entries == SIZE_MAX ? 0 : s.order.entries;  // (profiling's byte count only)
+      X.stage = MsmStage::Sorted;
+    }
+    if (nj == 2) {
+      J[0].buckets = (G1Xyzz *)run.msm.buckets.ensure(sizeof(G1Xyzz) * 2 * P.nb);
+      J[1].buckets = J[0].buckets + P.nb;
+    }
+    for (int j = 0; j < nj; j++) msm_launch_accumulate(ctx, J[j], nullptr, run.stream);
+    MsmJob *both[2] = {&J[0], &J[1]};
+    msm_launch_tails(ctx, both, nj, run);
+    for (int j = 0; j < nj; j++) {
+      out.window_sums[j] = msm_window_sums(ctx, J[j]);
+      out.result[j] = msm_horner(P, out.window_sums[j]);
+      out.buckets[j] = J[j].buckets;
+      out.fix_levels[j] = J[j].fix_levels;
+    }
+    out.tail = J[0].tail;
+  } catch (...) {  // nothing queued here still runs on the caller's buffers
+    (void)hipStreamSynchronize(run.stream);
+    throw;
+  }
 }
 
 // ---------------------------------------------------------------- a batch over one base

@@ -163,6 +163,25 @@ void lane_publish_slot(MsmLane &ln, int slot, uint32_t **data, uint32_t **flag, 
 // fb_off: the points are entries [fb_off, fb_off + n) of the set fb was built for
 G1Xyzz msm_dev(Ctx *c, const G1Affine *points, const Fr *scalars, size_t n, const FixedBase *fb = nullptr,
                size_t fb_off = 0);
+// An MSM from a given bucket order: the accumulation with its fix-up, the bucket reduction and the
+// host finish, without the scalar prep and the sort (tests/device/accprobe.hip hands it orders no
+// affordable scalar vector produces).  One set, or two of the same shared-layout plan whose tails
+// run as one two-set launch sequence, as a pair of table-plan openings.
+struct OrderedSet {
+  BucketOrder order;       // device; keys optional (with ks), entries unused
+  uint32_t *valid;         // device, two words as the sort leaves them: [0] the entries, [1] = 0
+  const G1Affine *points;  // what the values index
+  int acc_k;               // entries per accumulation chunk
+  size_t nchunks;          // acc_k nchunks >= the entries (chunks past them are skipped)
+};
+struct OrderedMsm {
+  G1Xyzz result[2];
+  std::vector<G1Xyzz> window_sums[2];  // per set, before Horner: P.Wr points
+  G1Xyzz *buckets[2];                  // device: P.nb buckets after the fix-up, lazy domain
+  TailGeom tail;                       // the reduction's geometry as run
+  int fix_levels[2];                   // fix levels built per set
+};
+void msm_from_order_dev(Ctx *c, const MsmPlan &P, const OrderedSet *sets, int nj, OrderedMsm &out);
 // how the scalars of one MSM of a pair get ready and in which form the sort reads them
 struct ScalarSource {
   // enqueued on the lane's stream before anything else of this MSM: produces the scalars

@@ -219,4 +219,71 @@ inline SortGeom sort_geom(size_t n, const WindowPlan &plan) {
   return g;
 }
 
+// ---------------------------------------------------------------- the accumulation's tail
+// What msm.hip's fix-up and bucket reduction derive from numbers alone (tests/test_accref_cpu.py
+// walks every legal plan through it; DESIGN 2.16 has the table of what occurs).
+constexpr int RED_L = 16;   // running-sum group size of the bucket reduction (sets of more than 2^19 buckets)
+constexpr int FIX_FAN = 8;  // short peel chains: single-thread add chains are latency-bound
+constexpr int FIX_LEVELS = 8;
+// runs over more chunks than this are summed by a whole wave in k_bucket_fixup, shorter ones by one thread
+constexpr size_t FIX_WAVE_SPAN = 512;
+
+// The fix-up's level sizes for an accumulation of nchunks chunks: level l >= 1 has len[l] =
+// nchunks / FIX_FAN^l groups and exists while that is >= 2 (a run climbs to a level only over two
+// aligned groups of it); total: the groups of all levels, one allocation.
+struct FixLevelSizes {
+  int n = 0;  // levels built (0: none)
+  size_t len[FIX_LEVELS + 1] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  size_t total = 0;
+};
+inline FixLevelSizes fix_level_sizes(size_t nchunks) {
+  FixLevelSizes F;
+  for (size_t groups = nchunks / FIX_FAN; F.n < FIX_LEVELS && groups >= 2; groups /= FIX_FAN) {
+    F.len[++F.n] = groups;
+    F.total += groups;
+  }
+  return F;
+}
+
+// The bucket reduction of sets of `half` buckets (msm.hip's header, steps 5 and 6): running sums
+// over groups of L0 buckets, then the weighted group sum  sum_g g S_g = sum_b 2^b M_b,
+// M_b = sum_{g: bit b of g} S_g,  as nbits + 2 plain sums (the M_b and sum_g T_g in two halves) --
+// short dependency chains only.  Up to 2^19 buckets per set the chains are the latency: groups of 4
+// and masked-sum chunks of 8 (C2, 2^20 points: 2.73 -> 2.65 ms); from 2^21 buckets groups of 16 stay
+// the fastest (2^22, 2^24; 8: +0.19 ms, 32: +0.63 ms per C4 step, r05 A/B).  c >= 4: half >= 8, so g >= 2.
+struct TailGeom {
+  int L0 = 0;      // k_reduce_level's group
+  int L1 = 0;      // k_reduce_level2's group (0: no second level)
+  size_t g1 = 0;   // first-level groups per set
+  size_t g = 0;    // groups the masked sums run over
+  int nbits = 0, specs = 0;  // bits of a group index; sums per set (nbits masked + 2 halves of T)
+  int CH = 0;      // items per masked-sum chunk
+  size_t nch = 0;  // chunks per spec
+  bool tree = false;  // k_masked_sums adds each wave's 64 chunk sums by a butterfly
+  int lg0 = 0;     // log2 L0 (k_reduce_level2's doublings)
+  int weight = 0;  // of the masked sums: L0, or L0 L1 with a second level (the host finish's doublings)
+  size_t sum_n = 0;  // parts per spec that sum_sets adds
+};
+inline TailGeom tail_geom(size_t half) {
+  TailGeom t;
+  const bool small_sets = half <= ((size_t)1 << 19);
+  t.L0 = (int)std::min<size_t>(small_sets ? 4 : RED_L, half / 2);
+  t.g1 = half / t.L0;
+  // a second level (k_reduce_level2, groups of L1 = 4) when the first leaves many groups
+  t.L1 = t.g1 >= ((size_t)1 << 13) ? 4 : 0;
+  if (t.L1 && t.g1 / t.L1 < 2) t.L1 = 0;
+  t.g = t.L1 ? t.g1 / t.L1 : t.g1;
+  while (((size_t)1 << t.nbits) < t.g) t.nbits++;
+  t.specs = t.nbits + 2;
+  while ((1 << t.lg0) < t.L0) t.lg0++;
+  t.weight = t.L1 ? t.L0 * t.L1 : t.L0;
+  t.CH = (int)std::min<size_t>(small_sets || t.L1 ? 8 : 16, t.g / 2);
+  t.nch = t.g / (2 * (size_t)t.CH);
+  t.tree = t.nch % 64 == 0;
+  t.sum_n = t.tree ? t.nch / 64 : t.nch;
+  return t;
+}
+// sum_sets (msm.hip) adds n parts per set: 8-way k_sum_chunks passes while this holds, then k_set_sum
+inline bool sum_sets_splits(size_t n) { return n > 128 && n % 8 == 0; }
+
 }  // namespace tns
